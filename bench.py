@@ -2,7 +2,7 @@
 """bench.py -- G+D training-step throughput of the pgan hot path on MI355X (BASELINE.json metric:
 3D volumes/sec/node at 128x128x32).
 
-  python bench.py --gpus N --steps K --warmup W [--config 1..5]
+  python bench.py --gpus N --steps K --warmup W [--config 1..5] [--dump-outputs DIR]
 
 N == 1 runs in this process.  N > 1: under torch.distributed.run (RANK / WORLD_SIZE in the environment) this process
 IS one rank; started plainly, bench.py spawns N fresh rank processes itself (before anything touches a GPU), waits for
@@ -20,6 +20,12 @@ Rank 0 prints ONE JSON line.  At N == 1 on the default workload the same line al
 of the same workload and the rate with the `.npy` loader (NumpyPathDataset + PinnedPrefetcher over synthetic files)
 inside the timed loop, and `cpu_baseline`: whole G+D steps of the CPU oracle timed on this host.
 
+--dump-outputs DIR writes what the last timed step computed (the G and D variables and their EMA shadows) as float32 .npy
+files, under 64 MB in all: a fixed sample when the networks are larger (workload.dump_outputs).  With the same arguments the
+inputs are the same on every run (seeded weights, batches and random source; the settle steps are rewound), so two builds can
+be compared output for output.  (The weight gradients add with f32 atomics: runs agree to summation order, or bit for bit
+under SG_DETERMINISTIC=1.)
+
 This file holds the step and the timed region; the rest is in benchlib/: launch.py (arguments, rank spawning, --dry-run),
 workload.py (networks, optimizers, synthetic batches, the state the legs start from), legs.py (the timed region's bracket, the
 settle and calibration steps, the extra legs, the CPU baseline -- the only place outside tests/ and smoke() that imports oracle/),
@@ -34,8 +40,8 @@ sys.path.insert(0, ROOT)
 
 from benchlib import legs, roofline                                          # noqa: E402
 from benchlib.launch import CONFIGS, dry_run, parse, spawn_ranks             # noqa: E402,F401
-from benchlib.workload import (build, conv_flops_per_volume, restore_state,  # noqa: E402,F401
-                               snapshot_state, synthetic_batch, synthetic_volume)
+from benchlib.workload import (build, conv_flops_per_volume, dump_outputs,  # noqa: E402,F401
+                               restore_state, snapshot_state, synthetic_batch, synthetic_volume)
 
 # The host enqueues a step in ~10 ms and the device runs it in ~58: unthrottled, a long run has the host hundreds of steps ahead and
 # the caching allocator cannot hand blocks back that are still queued (700 steps ended in an out-of-memory error at 278 GiB).  The
@@ -121,6 +127,8 @@ def main():
     timed = roofline.collect(lib)
     lib.sg_prof_enable(0)
     lib.sg_prof_set_filter(0, None)
+    if args.dump_outputs and rank == 0:      # the state the K-th timed step left, before the loss step below moves it on
+        dump_outputs(cfg, args.dump_outputs)
     losses = [float(v) for v in sess.run(cfg['losses'] + cfg['train'], feed_dict={ph: batches[0]})[:2]]
     if not all(l == l and abs(l) < 1e30 for l in losses):
         raise SystemExit(f'non-finite losses after the timed steps: {losses}')

@@ -43,7 +43,14 @@ def parse():
     ap.add_argument('--cpu-budget-s', type=float, default=14.0)
     ap.add_argument('--dry-run', action='store_true',
                     help='plumbing rehearsal of the N-rank launch on CPU tensors over gloo: no GPU, no throughput (see dry_run)')
+    ap.add_argument('--dump-outputs', metavar='DIR', default=None,
+                    help='after the timed steps, write what the last one computed (G and D variables, EMA shadows; a fixed '
+                         'sample of them when large) as DIR/<name>.npy, float32 (workload.dump_outputs)')
     args = ap.parse_args()
+    if args.steps < 1:
+        ap.error('--steps must be at least 1')
+    if args.dump_outputs and args.dry_run:
+        ap.error('--dump-outputs needs the GPU step: the dry run computes no outputs')
     c = CONFIGS[args.config]
     for k in ('size', 'phase', 'latent', 'batch', 'dtype', 'alpha'):
         if getattr(args, k) is None:

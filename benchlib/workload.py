@@ -39,7 +39,8 @@ def build(args, device, dtype):
     base_shape, ks, fs = specs(args)
     rank = parallel.rank()
     store = VariableStore(device, seed=42)            # same initial weights on every rank (then broadcast anyway)
-    L.set_random_source(L.RandomSource(42 + rank, device))
+    rng = L.RandomSource(42 + rank, device)
+    L.set_random_source(rng)
     alpha = ScalarVariable(args.alpha, 'alpha')
     g_lr, d_lr = ScalarVariable(1e-3, 'g_lr'), ScalarVariable(1e-3, 'd_lr')
     og, od = opt.AdamOptimizer(g_lr, 0.0, 0.9), opt.AdamOptimizer(d_lr, 0.0, 0.9)
@@ -64,7 +65,7 @@ def build(args, device, dtype):
     sess = opt.Session(device)
     tg, td = (tup[12], tup[16]) if freeze is not None else (tup[0], tup[1])
     return dict(store=store, sess=sess, ph=ph, train=[tg, td], ema_op=ema.apply(), ks=ks, fs=fs,
-                base_shape=base_shape, shape=ph.shape, losses=[tup[3], tup[2]], graph=graph, optimizers=(og, od))
+                base_shape=base_shape, shape=ph.shape, losses=[tup[3], tup[2]], graph=graph, optimizers=(og, od), rng=rng)
 
 
 def synthetic_volume(shape, idx):
@@ -116,13 +117,16 @@ def conv_flops_per_volume(ks, fs, phase, base_shape, latent, dims=3):
 
 
 def snapshot_state(cfg):
-    """Parameters (flat buffers: the variables are views of them) and optimizer state after the warm-up: every extra leg
-    starts from here, as the main loop did, instead of continuing a trajectory that diverges further with every leg."""
+    """Parameters (flat buffers: the variables are views of them), their EMA shadows, optimizer state and the random source
+    (latents, mixing weights, instance-noise offsets) after the warm-up: every extra leg starts from here, as the main loop did,
+    instead of continuing a trajectory that diverges further with every leg.  The timed steps start from the same state and
+    draw the same random inputs on every run, however many settle steps the board needed."""
     import torch
     flat = {p: f['param'].detach().clone() for p, f in cfg['store'].flat.items()}
+    ema = {p: cfg['graph'].ema.shadow_flat(p).detach().clone() for p in cfg['store'].flat}
     opt = [(o.t, {p: {k: (v.detach().clone() if torch.is_tensor(v) else v) for k, v in st.items()} for p, st in o.state.items()})
            for o in cfg['optimizers']]
-    return dict(flat=flat, opt=opt)
+    return dict(flat=flat, ema=ema, opt=opt, rng=(cfg['rng'].gen.get_state(), cfg['rng'].calls))
 
 
 def restore_state(cfg, snap):
@@ -130,11 +134,45 @@ def restore_state(cfg, snap):
     with torch.no_grad():
         for p, t in snap['flat'].items():
             cfg['store'].flat[p]['param'].copy_(t)
+        for p, t in snap['ema'].items():
+            cfg['graph'].ema.shadow_flat(p).copy_(t)
         for o, (t_, st) in zip(cfg['optimizers'], snap['opt']):
             o.t = t_
             for p, d in st.items():
                 for k, v in d.items():
                     if torch.is_tensor(v):
                         o.state[p][k].copy_(v)
+    cfg['rng'].gen.set_state(snap['rng'][0])
+    cfg['rng'].calls = snap['rng'][1]
     from saragan_amd import functional as F
     F.clear_pack_cache()
+
+
+DUMP_BUDGET_BYTES = 60 * 10 ** 6      # --dump-outputs writes at most this much (under 64 MB)
+
+
+def dump_outputs(cfg, out_dir):
+    """--dump-outputs DIR: what a training step hands its caller -- the G and D variables and their EMA shadows -- as float32
+    DIR/generator.npy, DIR/generator_ema.npy, DIR/discriminator.npy, DIR/discriminator_ema.npy: the variables in the order of
+    the network's flat parameter buffer, flattened and concatenated (no padding).  A network larger than its share of DUMP_BUDGET_BYTES is sampled: the same fraction of
+    every variable (at least 64 entries of each), at sorted positions seeded by the variable's name, so two runs or two builds
+    dump the same entries."""
+    import zlib
+    import numpy as np
+    import torch
+    os.makedirs(out_dir, exist_ok=True)
+    prefixes = ('generator/', 'discriminator/')
+    cap = DUMP_BUDGET_BYTES // 4 // (2 * len(prefixes))      # float32 entries per file
+    ema = cfg['graph'].ema
+    for prefix in prefixes:
+        flat = cfg['store'].flat[prefix]
+        total = sum(n for _, n in flat['offsets'].values())
+        pos = []
+        for name, (o, n) in flat['offsets'].items():
+            m = n if total <= cap else min(n, max(64, n * cap // total))
+            pick = np.arange(n) if m == n else np.sort(np.random.default_rng(zlib.crc32(name.encode())).choice(n, m, replace=False))
+            pos.append(o + pick)
+        idx = torch.from_numpy(np.concatenate(pos)).to(flat['param'].device)
+        for suffix, buf in (('', flat['param']), ('_ema', ema.shadow_flat(prefix))):
+            np.save(os.path.join(out_dir, prefix.rstrip('/') + suffix + '.npy'),
+                    buf.detach().index_select(0, idx).to(torch.float32).cpu().numpy())

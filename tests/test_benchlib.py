@@ -1,7 +1,7 @@
 """benchlib/ (the parts of bench.py outside the timed region) on fabricated profiler tables: the dominant kernel is chosen by summed
 time per kernel name, the roofline object prices it against the right roof (MFMA above the machine balance, HBM below), the
-16x16x32 kernels are priced against that shape's measured ceiling, and the traffic lookup reads the newest committed counter file.
-No GPU."""
+16x16x32 kernels are priced against that shape's measured ceiling, and the traffic lookup reads the newest committed counter file;
+--dump-outputs and the state the timed steps start from, on CPU stand-ins of the workload.  No GPU."""
 import json
 import os
 import sys
@@ -82,3 +82,73 @@ def test_configs_follow_baseline_json(monkeypatch):
     monkeypatch.setattr(sys, 'argv', ['bench.py', '--config', 'out_txt', '--batch', '4'])
     a = parse()
     assert (a.config, a.size, a.phase, a.batch) == (6, 'xs', 5, 4)
+
+
+def _dump_cfg():
+    """A stand-in for workload.build's dict: CPU variables in flat buffers (with the 16-byte padding), EMA shadows beside them."""
+    import torch
+    from saragan_amd.networks import loss as L
+    from saragan_amd.varstore import VariableStore
+    store = VariableStore('cpu', seed=3)
+    for name, shape in (('generator/dense/weight', (50, 61)), ('generator/dense/bias', (5,)),
+                        ('discriminator/conv/weight', (3, 3, 3, 4, 41)), ('discriminator/conv/bias', (7,))):
+        store.get(name, shape, 'normal')
+    shadows = {p: store.flatten(p)['param'] * 0.5 + 1.0 for p in ('generator/', 'discriminator/')}
+    return dict(store=store, graph=types.SimpleNamespace(ema=types.SimpleNamespace(shadow_flat=shadows.__getitem__)),
+                optimizers=[], rng=L.RandomSource(7, 'cpu')), shadows
+
+
+def test_dump_outputs_whole_when_small_and_a_fixed_sample_within_budget(tmp_path, monkeypatch):
+    import numpy as np
+    from benchlib import workload
+    cfg, shadows = _dump_cfg()
+    store = cfg['store']
+    workload.dump_outputs(cfg, str(tmp_path / 'whole'))
+    assert sorted(os.listdir(tmp_path / 'whole')) == ['discriminator.npy', 'discriminator_ema.npy', 'generator.npy', 'generator_ema.npy']
+    for prefix in ('generator/', 'discriminator/'):
+        got = np.load(tmp_path / 'whole' / (prefix[:-1] + '.npy'))
+        assert got.dtype == np.float32
+        want = np.concatenate([v.detach().numpy().ravel() for k, v in store.vars.items() if k.startswith(prefix)])
+        assert np.array_equal(got, want)            # the variables in creation order, no padding
+        ema = np.load(tmp_path / 'whole' / (prefix[:-1] + '_ema.npy'))
+        assert np.array_equal(ema, want * 0.5 + 1.0)
+
+    monkeypatch.setattr(workload, 'DUMP_BUDGET_BYTES', 4 * 4 * 1000)      # 1000 entries per file
+    for run in ('a', 'b'):
+        workload.dump_outputs(cfg, str(tmp_path / run))
+    total = 0
+    for f in sorted(os.listdir(tmp_path / 'a')):
+        a, b = np.load(tmp_path / 'a' / f), np.load(tmp_path / 'b' / f)
+        assert np.array_equal(a, b) and a.dtype == np.float32
+        total += a.size
+        assert 1000 <= a.size <= 1000 + 64 * 2
+    assert total * 4 <= workload.DUMP_BUDGET_BYTES + 4 * 64 * 2 * 4
+    # every sampled entry is an entry of the buffer, the small bias is there whole, and the EMA file samples the same positions
+    g = np.load(tmp_path / 'a' / 'generator.npy')
+    w = store.vars['generator/dense/weight'].detach().numpy().ravel()
+    assert np.isin(g[:-5], w).all() and np.array_equal(g[-5:], store.vars['generator/dense/bias'].detach().numpy())
+    assert np.array_equal(np.load(tmp_path / 'a' / 'generator_ema.npy'), g * 0.5 + 1.0)
+
+
+def test_restore_state_rewinds_the_weights_the_ema_and_the_random_source():
+    """The settle steps run a time-dependent number of steps: after restore_state the timed steps start from the weights and EMA
+    shadows of the end of the warm-up and draw the random inputs the first step after it would have drawn."""
+    import torch
+    from benchlib import workload
+    cfg, shadows = _dump_cfg()
+    rng, flat = cfg['rng'], cfg['store'].flat
+    rng.latent(4, 8, 'cpu')
+    rng.calls = 3
+    snap = workload.snapshot_state(cfg)
+    w0, s0 = flat['generator/']['param'].clone(), shadows['discriminator/'].clone()
+    z, g = rng.latent(4, 8, 'cpu'), rng.gamma(4, 'cpu')
+    for _ in range(5):             # settle steps
+        rng.latent(4, 8, 'cpu')
+        rng.gamma(4, 'cpu')
+        rng.calls += 2
+        flat['generator/']['param'].add_(1.0)
+        shadows['discriminator/'].mul_(0.9)
+    workload.restore_state(cfg, snap)
+    assert rng.calls == 3
+    assert torch.equal(rng.latent(4, 8, 'cpu'), z) and torch.equal(rng.gamma(4, 'cpu'), g)
+    assert torch.equal(flat['generator/']['param'], w0) and torch.equal(shadows['discriminator/'], s0)
