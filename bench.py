@@ -2,7 +2,7 @@
 """bench.py -- G+D training-step throughput of the pgan hot path on MI355X (BASELINE.json metric:
 3D volumes/sec/node at 128x128x32).
 
-  python bench.py --gpus N --steps K --warmup W [--config 1..5] [--dump-outputs DIR]
+  python bench.py --gpus N --steps K --warmup W [--config 1..5] [--dump-outputs DIR] [--full]
 
 N == 1 runs in this process.  N > 1: under torch.distributed.run (RANK / WORLD_SIZE in the environment) this process
 IS one rank; started plainly, bench.py spawns N fresh rank processes itself (before anything touches a GPU), waits for
@@ -16,9 +16,12 @@ f32 master weights, WGAN-GP (gp 10), stabilising phase (alpha 0), per-GPU batch 
 --config selects the other BASELINE configurations (1: xs phase 1 fp32 batch 4; 2: xs phase 4 bf16 batch 32;
 4: 'm' phase 7 with fade-in, batch 2; 5: 2-D pgan 1024^2 fp32).
 
-Rank 0 prints ONE JSON line.  At N == 1 on the default workload the same line also carries (`extras`) the fp32 rate
-of the same workload and the rate with the `.npy` loader (NumpyPathDataset + PinnedPrefetcher over synthetic files)
-inside the timed loop, and `cpu_baseline`: whole G+D steps of the CPU oracle timed on this host.
+Rank 0 prints ONE JSON line.  A plain run does only what that line's headline needs: set-up, the W warm-up steps, the settle
+and calibration steps, the K timed steps (with the dominant kernel's roofline, bracketed inside them), the outputs, the line.
+--full adds what takes runs of its own, after the timed steps: at N == 1 on the default workload the line then also carries
+(`extras`) the fp32 rate of the same workload, the rate with the faded-out branch computed and the rate with the `.npy` loader
+(NumpyPathDataset + PinnedPrefetcher over synthetic files) inside the timed loop, and at N == 1 `cpu_baseline`: whole G+D
+steps of the CPU oracle timed on this host (--no-extras / --no-cpu-baseline leave either out).
 
 --dump-outputs DIR writes what the last timed step computed (the G and D variables and their EMA shadows) as float32 .npy
 files, under 64 MB in all: a fixed sample when the networks are larger (workload.dump_outputs).  With the same arguments the
@@ -173,7 +176,7 @@ def main():
     small = roofline.small_channel_object(table, args.dtype)
     if small:
         out['roofline_hbm'] = small
-    if world == 1 and args.config == 3 and not args.no_extras:
+    if args.full and world == 1 and args.config == 3 and not args.no_extras:
         cpu_cfg = dict(ks=cfg['ks'], fs=cfg['fs'], base_shape=cfg['base_shape'], shape=cfg['shape'])      # (what cpu_baseline needs, kept past the legs)
         extras = {}
         try:
@@ -192,7 +195,7 @@ def main():
             extras['error'] = repr(exc)[:300]
         out['extras'] = extras
         cfg = cpu_cfg
-    if world == 1 and not args.no_cpu_baseline:
+    if args.full and world == 1 and not args.no_cpu_baseline:
         try:
             out['cpu_baseline'] = legs.cpu_baseline(args, cfg, args.cpu_budget_s)
         except Exception as exc:      # (reported, never fatal for the line)

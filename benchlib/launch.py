@@ -37,8 +37,11 @@ def parse():
     ap.add_argument('--dtype', default=None, choices=['bf16', 'f32'])
     ap.add_argument('--loss', default='wgan', choices=['wgan', 'logistic'])
     ap.add_argument('--alpha', type=float, default=None, help='0: stabilising phase; >0: mixing (freeze ops)')
-    ap.add_argument('--no-cpu-baseline', action='store_true')
-    ap.add_argument('--no-extras', action='store_true', help='skip the fp32 and loader-in-the-loop legs')
+    ap.add_argument('--full', action='store_true',
+                    help='after the headline line\'s measurement, also run the extra legs (loader in the loop, fade branch '
+                         'computed, fp32; default workload, one GPU) and the CPU baseline (one GPU) and report them in the line')
+    ap.add_argument('--no-cpu-baseline', action='store_true', help='with --full: skip the CPU baseline')
+    ap.add_argument('--no-extras', action='store_true', help='with --full: skip the fp32, fade and loader-in-the-loop legs')
     ap.add_argument('--dump-prof', action='store_true', help='per-shape conv kernel table on stderr')
     ap.add_argument('--cpu-budget-s', type=float, default=14.0)
     ap.add_argument('--dry-run', action='store_true',

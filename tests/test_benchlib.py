@@ -84,6 +84,14 @@ def test_configs_follow_baseline_json(monkeypatch):
     assert (a.config, a.size, a.phase, a.batch) == (6, 'xs', 5, 4)
 
 
+def test_extra_legs_and_cpu_baseline_only_with_full(monkeypatch):
+    monkeypatch.setattr(sys, 'argv', ['bench.py', '--gpus', '1', '--steps', '20', '--warmup', '5'])
+    assert parse().full is False
+    monkeypatch.setattr(sys, 'argv', ['bench.py', '--full', '--no-cpu-baseline'])
+    a = parse()
+    assert a.full and a.no_cpu_baseline and not a.no_extras
+
+
 def _dump_cfg():
     """A stand-in for workload.build's dict: CPU variables in flat buffers (with the 16-byte padding), EMA shadows beside them."""
     import torch

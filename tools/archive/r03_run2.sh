@@ -8,12 +8,12 @@ mkdir -p $O
 run() { local t=$1; shift; timeout -k 10 "$t" "$@"; local rc=$?; if [ $rc -eq 124 ] || [ $rc -eq 137 ]; then echo "TIMEOUT: $*"; exit 1; fi; return $rc; }
 export SARAGAN_BENCH_MARK=1
 cd /tmp && export TMPDIR=/tmp && cd "$GRAFT_REPO_ROOT"
-run 400 rocprofv3 --kernel-trace --output-format csv -d $O/trace -- python3 bench.py --no-cpu-baseline --steps 10 > $O/bench_traced.json 2> $O/bench_traced.err
+run 400 rocprofv3 --kernel-trace --output-format csv -d $O/trace -- python3 bench.py --full --no-cpu-baseline --steps 10 > $O/bench_traced.json 2> $O/bench_traced.err
 f=$(ls $O/trace/*/*kernel_trace.csv | head -1); echo "trace: $f $(wc -l < $f) rows"
 python tools/trace_windows.py "$f" > $O/leg_windows.txt 2>&1; head -60 $O/leg_windows.txt
 gzip -9 -c "$f" > $O/kernel_trace.csv.gz; rm -rf $O/trace
 unset SARAGAN_BENCH_MARK
-SARAGAN_BENCH_NO_PROF=1 run 300 python bench.py --no-cpu-baseline --steps 20 --warmup 5 > $O/bench_noprof.json 2> $O/bench_noprof.err; python - <<'PY'
+SARAGAN_BENCH_NO_PROF=1 run 300 python bench.py --full --no-cpu-baseline --steps 20 --warmup 5 > $O/bench_noprof.json 2> $O/bench_noprof.err; python - <<'PY'
 import json
 for f in ('bench_traced','bench_noprof'):
     try:

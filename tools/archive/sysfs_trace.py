@@ -44,7 +44,7 @@ def main():
     th = threading.Thread(target=sampler, daemon=True)
     th.start()
     env = dict(os.environ, SARAGAN_BENCH_MARK='1')
-    p = subprocess.run([sys.executable, os.path.join(ROOT, 'bench.py'), '--no-cpu-baseline'] + sys.argv[1:], env=env,
+    p = subprocess.run([sys.executable, os.path.join(ROOT, 'bench.py'), '--full', '--no-cpu-baseline'] + sys.argv[1:], env=env,
                        capture_output=True, text=True, timeout=600)
     stop.set()
     th.join()

@@ -22,7 +22,7 @@ kill $SMI
 cp $R/gpurun_out/pmc_manifest.json $O/pmc_manifest.json
 run 300 rocprofv3 --kernel-trace --stats --output-format csv -d $O/prof_bench -o bench -- python3 $R/bench.py --steps 10 --warmup 3 --no-extras --no-cpu-baseline > $O/prof_bench.log 2>&1 || exit 1
 cd $R
-run 300 python bench.py --steps 20 --warmup 5 > $O/bench_default.json 2> $O/bench_default.err
+run 300 python bench.py --steps 20 --warmup 5 --full > $O/bench_default.json 2> $O/bench_default.err
 run 200 python bench.py --dump-prof --steps 5 --warmup 3 --no-extras --no-cpu-baseline > /dev/null 2> $O/bench_conv_table.txt
 for c in 1 2 4 5; do run 200 python bench.py --config $c --steps 20 --warmup 5 --no-cpu-baseline > $O/bench_config$c.json 2> $O/bench_config$c.err; done
 # the reference's own operating point (out.txt: xs phase 5, 64x64x16) at local batch 2 / 4 / 8, and the headline network at 2 / 4
