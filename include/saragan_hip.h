@@ -386,6 +386,28 @@ int sg_optim_step_dev(int kind, float* p, const float* g, float* s1, float* s2, 
 /* out[i] = sum of squares of segment i (offsets[i]..offsets[i+1]) of a flat f32 buffer
  * (tf.norm per gradient + tf.clip_by_global_norm, optimization.py:66-71).  offsets: DEVICE int64[nseg+1]. */
 int sg_segment_sumsq(const float* flat, const int64_t* offsets, float* out, int32_t nseg, sg_stream_t st);
+/* Non-finite step guard (not in the reference; optimization.StepGraph with the guard on).  A train op whose gradient holds a
+ * NaN or +-Inf after the data-parallel reduction does nothing this step: parameters, optimiser state and step count stay
+ * as they were, the EMA update still runs.  All flags are DEVICE int32 (0 = all finite), all counters DEVICE int64.
+ * sg_nonfinite_flag: *flag = 1 if any x[i] is non-finite (isfinite, not an overflow test: 3e38 is finite); accumulate = 0
+ * clears *flag first (a memset on `st`), 1 ORs into it (several ranges of one network).  x 16-byte aligned.
+ * sg_segment_sumsq_flag: sg_segment_sumsq that also sets *flag from the values it reads (the clipping path: no second pass).
+ * sg_guard_step (one thread): flag clear -> ++*t, counters[1] = 0, *lr_t = adam ? (float)(lr*sqrt(1-b2^t)/(1-b1^t)) in
+ * double : (float)lr; flag set -> ++counters[0], ++counters[1], counters[2] = max(counters[2], counters[1]).
+ * counters: [skipped, consecutive skips, longest run].  lr_dev (may be NULL): a DEVICE double read instead of lr (captured
+ * step: the host writes the base learning rate before each replay).
+ * sg_adam_ema_guarded / sg_optim_step_guarded: sg_adam_ema_dev / sg_optim_step_dev with a skip flag: clear -> exactly their
+ * result with the step size *lr_t / *lr; set -> the EMA-only update (sg_adam_ema with g NULL), or nothing if ema is NULL. */
+int sg_nonfinite_flag(const float* x, int64_t numel, int32_t* flag, int32_t accumulate, sg_stream_t st);
+int sg_segment_sumsq_flag(const float* flat, const int64_t* offsets, float* out, int32_t nseg, int32_t* flag,
+                          int32_t accumulate, sg_stream_t st);
+int sg_guard_step(const int32_t* flag, int64_t* t, int64_t* counters, double lr, const double* lr_dev, float* lr_t,
+                  int32_t adam, double b1, double b2, sg_stream_t st);
+int sg_adam_ema_guarded(float* p, const float* g, float* m, float* v, float* ema, int64_t numel, const float* lr_t,
+                        const int32_t* skip, float b1, float b2, float eps, float gscale, float ema_decay, sg_stream_t st);
+int sg_optim_step_guarded(int kind, float* p, const float* g, float* s1, float* s2, float* ema, int64_t numel,
+                          const float* lr, const int32_t* skip, float h, float eps, int nesterov, float gscale,
+                          float ema_decay, sg_stream_t st);
 
 /* ---- validation metrics on device tensors (metrics/swd.py:13-123, metrics/skim_metrics.py:8-45) ---------------- */
 /* One axis of a separable FIR filter over x viewed as [outer, n, inner] (f32, or f64 when `f64` != 0; accumulated in

@@ -24,3 +24,22 @@ def set_deterministic(on=True):
     # not clear the slabs it read): none survives a switch
     from . import functional as F
     F.clear_kept_workspaces()
+
+
+def set_nonfinite_guard(on=True, max_consecutive=None):
+    """Non-finite step guard (not in the reference; off by default): a train op whose gradient, after the data-parallel
+    reduction and before clipping, holds a NaN or +-Inf does nothing that step -- parameters, optimiser slots and the
+    optimiser's step count stay as they were, the EMA update still runs -- decided on the device inside the (captured)
+    step.  Applies to step graphs built afterwards (as SARAGAN_NONFINITE_GUARD=1 does); graph.skipped_steps counts the
+    skips.  max_consecutive: graph.check_nonfinite raises NonFiniteStepsError once one network was skipped that many times
+    in a row (train.py checks at its sync points)."""
+    import os
+    if max_consecutive is not None and not on:
+        raise ValueError('max_consecutive needs the guard on')
+    if max_consecutive is not None and int(max_consecutive) < 1:
+        raise ValueError('max_consecutive must be >= 1')
+    os.environ['SARAGAN_NONFINITE_GUARD'] = '1' if on else '0'
+    if max_consecutive is None:
+        os.environ.pop('SARAGAN_NONFINITE_MAX_CONSECUTIVE', None)
+    else:
+        os.environ['SARAGAN_NONFINITE_MAX_CONSECUTIVE'] = str(int(max_consecutive))

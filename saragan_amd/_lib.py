@@ -106,6 +106,11 @@ SIGNATURES = {
     'sg_adam_ema_dev': (C.c_int, [_p, _p, _p, _p, _p, _i64, _p, _f, _f, _f, _f, _f, _p]),
     'sg_optim_step_dev': (C.c_int, [C.c_int, _p, _p, _p, _p, _p, _i64, _p, _f, _f, C.c_int, _f, _f, _p]),
     'sg_segment_sumsq': (C.c_int, [_p, _p, _p, _i32, _p]),
+    'sg_nonfinite_flag': (C.c_int, [_p, _i64, _p, _i32, _p]),
+    'sg_segment_sumsq_flag': (C.c_int, [_p, _p, _p, _i32, _p, _i32, _p]),
+    'sg_guard_step': (C.c_int, [_p, _p, _p, C.c_double, _p, _p, _i32, C.c_double, C.c_double, _p]),
+    'sg_adam_ema_guarded': (C.c_int, [_p, _p, _p, _p, _p, _i64, _p, _p, _f, _f, _f, _f, _f, _p]),
+    'sg_optim_step_guarded': (C.c_int, [C.c_int, _p, _p, _p, _p, _p, _i64, _p, _p, _f, _f, C.c_int, _f, _f, _p]),
     'sg_filter_axis': (C.c_int, [_p, _p, _p, _i64, _i32, _i64, C.POINTER(C.c_double), _i32, _i32, _i32, C.c_double, _i32, _p]),
     'sg_swd_gather': (C.c_int, [_p, _p, _p, _p, _p, _i32, _i32, _i32, _i32, _i32, _i32, _i32, _i32, _i32, _p]),
     'sg_desc_normalize_workspace': (_sz, [_i32]),

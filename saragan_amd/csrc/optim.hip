@@ -2,14 +2,19 @@
 // (gradient norms / global-norm clipping).  Reference: tf.train.AdamOptimizer as called at
 // SURFGAN_3D/optimization.py:16,28; tf.train.ExponentialMovingAverage via ExtendedEMA.py:56-59;
 // tf.norm / tf.clip_by_global_norm at optimization.py:66-71.  One pass: 5 reads + 4 writes of 4 B/param.
+//
+// Non-finite step guard (not in the reference; off by default, optimization.StepGraph): an all-finite test over a network's
+// flat gradient (alone, or fused into the sum of squares of the clipping path) sets a device flag; a one-thread bookkeeping
+// kernel advances the optimiser's device step count and writes the step size only when the flag is clear; the guarded
+// update kernels read the flag and then either compute exactly what the unguarded ones compute or take the EMA-only path.
+// Flags are set with plain stores of the value 1 (any order gives the same result: deterministic).
 #include "common.h"
 
 namespace {
 
-__global__ void adam_ema_kernel(float* __restrict__ p, const float* __restrict__ g, float* __restrict__ m,
-                                float* __restrict__ v, float* __restrict__ ema, int64_t numel, float lr_t, float b1,
-                                float b2, float eps, float gscale, float ema_decay, const float* __restrict__ lr_dev) {
-  if (lr_dev) lr_t = *lr_dev;      // captured step: the bias-corrected step size is written by the host before each replay
+__device__ __forceinline__ void adam_ema_body(float* __restrict__ p, const float* __restrict__ g, float* __restrict__ m,
+                                              float* __restrict__ v, float* __restrict__ ema, int64_t numel, float lr_t,
+                                              float b1, float b2, float eps, float gscale, float ema_decay) {
   const int64_t nv = numel / 4;
   const int64_t tid0 = (int64_t)blockIdx.x * blockDim.x + threadIdx.x, stride = (int64_t)gridDim.x * blockDim.x;
   const float omd = 1.f - ema_decay;
@@ -49,6 +54,24 @@ __global__ void adam_ema_kernel(float* __restrict__ p, const float* __restrict__
   }
 }
 
+__global__ void adam_ema_kernel(float* __restrict__ p, const float* __restrict__ g, float* __restrict__ m,
+                                float* __restrict__ v, float* __restrict__ ema, int64_t numel, float lr_t, float b1,
+                                float b2, float eps, float gscale, float ema_decay, const float* __restrict__ lr_dev) {
+  if (lr_dev) lr_t = *lr_dev;      // captured step: the bias-corrected step size is written by the host before each replay
+  adam_ema_body(p, g, m, v, ema, numel, lr_t, b1, b2, eps, gscale, ema_decay);
+}
+
+// Guarded step: a set skip flag turns the launch into the EMA-only one (g NULL), a clear one computes what adam_ema_kernel
+// computes with lr_t read from device memory (written by guard_step_kernel).
+__global__ void adam_ema_guard_kernel(float* __restrict__ p, const float* __restrict__ g, float* __restrict__ m,
+                                      float* __restrict__ v, float* __restrict__ ema, int64_t numel,
+                                      const float* __restrict__ lr_dev, float b1, float b2, float eps, float gscale,
+                                      float ema_decay, const int32_t* __restrict__ skip) {
+  const bool skipped = *skip != 0;
+  if (skipped && !ema) return;
+  adam_ema_body(p, skipped ? nullptr : g, m, v, ema, numel, skipped ? 0.f : *lr_dev, b1, b2, eps, gscale, ema_decay);
+}
+
 // tf.train.GradientDescentOptimizer / MomentumOptimizer(use_nesterov) / AdadeltaOptimizer(rho, epsilon) as created
 // at SURFGAN_3D/optimization.py:17-22,29-35, fused with the EMA update like Adam above.  TF's update rules
 // (training_ops: ApplyGradientDescent, ApplyMomentum, ApplyAdadelta):
@@ -72,10 +95,9 @@ __device__ __forceinline__ void optim_rule(float& p, float g, float& s1, float& 
 }
 
 template <int KIND>
-__global__ void optim_step_kernel(float* __restrict__ p, const float* __restrict__ g, float* __restrict__ s1,
-                                  float* __restrict__ s2, float* __restrict__ ema, int64_t numel, float lr, float h,
-                                  float eps, int nesterov, float gscale, float ema_decay, const float* __restrict__ lr_dev) {
-  if (lr_dev) lr = *lr_dev;
+__device__ __forceinline__ void optim_step_body(float* __restrict__ p, const float* __restrict__ g, float* __restrict__ s1,
+                                                float* __restrict__ s2, float* __restrict__ ema, int64_t numel, float lr,
+                                                float h, float eps, int nesterov, float gscale, float ema_decay) {
   const int64_t nv = numel / 4;
   const int64_t tid0 = (int64_t)blockIdx.x * blockDim.x + threadIdx.x, stride = (int64_t)gridDim.x * blockDim.x;
   const float omd = 1.f - ema_decay;
@@ -114,14 +136,93 @@ __global__ void optim_step_kernel(float* __restrict__ p, const float* __restrict
   }
 }
 
-__global__ __launch_bounds__(256) void segment_sumsq_kernel(const float* __restrict__ flat,
-                                                            const int64_t* __restrict__ offsets,
-                                                            float* __restrict__ out) {
+template <int KIND>
+__global__ void optim_step_kernel(float* __restrict__ p, const float* __restrict__ g, float* __restrict__ s1,
+                                  float* __restrict__ s2, float* __restrict__ ema, int64_t numel, float lr, float h,
+                                  float eps, int nesterov, float gscale, float ema_decay, const float* __restrict__ lr_dev) {
+  if (lr_dev) lr = *lr_dev;
+  optim_step_body<KIND>(p, g, s1, s2, ema, numel, lr, h, eps, nesterov, gscale, ema_decay);
+}
+
+// The EMA-only pass of a skipped step: the arithmetic of adam_ema_body's `g == NULL` path.
+__device__ __forceinline__ void ema_only_body(const float* __restrict__ p, float* __restrict__ ema, int64_t numel,
+                                              float ema_decay) {
+  const int64_t nv = numel / 4;
+  const int64_t tid0 = (int64_t)blockIdx.x * blockDim.x + threadIdx.x, stride = (int64_t)gridDim.x * blockDim.x;
+  const float omd = 1.f - ema_decay;
+  for (int64_t i = tid0; i < nv; i += stride) {
+    const f32x4 pp = reinterpret_cast<const f32x4*>(p)[i];
+    f32x4 ee = reinterpret_cast<f32x4*>(ema)[i];
+    ee -= omd * (ee - pp);
+    reinterpret_cast<f32x4*>(ema)[i] = ee;
+    SG_STORE16_GUARD(ee);
+  }
+  for (int64_t i = nv * 4 + tid0; i < numel; i += stride) ema[i] -= omd * (ema[i] - p[i]);
+}
+
+template <int KIND>
+__global__ void optim_step_guard_kernel(float* __restrict__ p, const float* __restrict__ g, float* __restrict__ s1,
+                                        float* __restrict__ s2, float* __restrict__ ema, int64_t numel,
+                                        const float* __restrict__ lr_dev, float h, float eps, int nesterov, float gscale,
+                                        float ema_decay, const int32_t* __restrict__ skip) {
+  if (*skip) {
+    if (ema) ema_only_body(p, ema, numel, ema_decay);
+    return;
+  }
+  optim_step_body<KIND>(p, g, s1, s2, ema, numel, *lr_dev, h, eps, nesterov, gscale, ema_decay);
+}
+
+__device__ __forceinline__ bool finite4(const f32x4 v) {
+  return __builtin_isfinite(v[0]) & __builtin_isfinite(v[1]) & __builtin_isfinite(v[2]) & __builtin_isfinite(v[3]);
+}
+
+// flag = 1 if any of x[0..numel) is NaN or +-Inf (the caller clears it first).  f32x4 loads, scalar tail for numel % 4.
+__global__ __launch_bounds__(256) void nonfinite_flag_kernel(const float* __restrict__ x, int64_t numel,
+                                                             int32_t* __restrict__ flag) {
+  const int64_t nv = numel / 4;
+  const int64_t tid0 = (int64_t)blockIdx.x * blockDim.x + threadIdx.x, stride = (int64_t)gridDim.x * blockDim.x;
+  bool ok = true;
+  for (int64_t i = tid0; i < nv; i += stride) ok &= finite4(reinterpret_cast<const f32x4*>(x)[i]);
+  for (int64_t i = nv * 4 + tid0; i < numel; i += stride) ok &= __builtin_isfinite(x[i]);
+  if (!ok) *flag = 1;
+}
+
+// One bookkeeping thread per guarded train op, between the flag and the update: an applied step advances the device step
+// count t and writes the step size the update reads (Adam: lr*sqrt(1-b2^t)/(1-b1^t) in double, as the host computes it,
+// then rounded to float; the other rules: lr); a skipped one counts.  cnt: [skipped, consecutive skips, longest run].
+__global__ void guard_step_kernel(const int32_t* __restrict__ flag, int64_t* __restrict__ t, int64_t* __restrict__ cnt,
+                                  double lr, const double* __restrict__ lr_dev, float* __restrict__ lr_t, int adam, double b1,
+                                  double b2) {
+  if (threadIdx.x != 0 || blockIdx.x != 0) return;
+  if (*flag) {
+    const int64_t run = cnt[1] + 1;
+    cnt[0] += 1;
+    cnt[1] = run;
+    if (run > cnt[2]) cnt[2] = run;
+    return;
+  }
+  if (lr_dev) lr = *lr_dev;
+  const int64_t s = *t + 1;
+  *t = s;
+  cnt[1] = 0;
+  *lr_t = adam ? (float)(lr * sqrt(1.0 - pow(b2, (double)s)) / (1.0 - pow(b1, (double)s))) : (float)lr;
+}
+
+// flag (may be NULL): the all-finite test of nonfinite_flag_kernel on the values this pass reads anyway.  It is a separate
+// test: a finite gradient whose squares overflow (3e38) is not flagged.
+__device__ __forceinline__ void segment_sumsq_body(const float* __restrict__ flat, const int64_t* __restrict__ offsets,
+                                                   float* __restrict__ out, int32_t* __restrict__ flag) {
   __shared__ float red[256];
   const int seg = blockIdx.x;
   const int64_t b = offsets[seg], e = offsets[seg + 1];
   float s = 0.f;
-  for (int64_t i = b + threadIdx.x; i < e; i += 256) s += flat[i] * flat[i];
+  bool ok = true;
+  for (int64_t i = b + threadIdx.x; i < e; i += 256) {
+    const float x = flat[i];
+    s += x * x;
+    if (flag) ok &= __builtin_isfinite(x);
+  }
+  if (flag && !ok) *flag = 1;
   red[threadIdx.x] = s;
   __syncthreads();
   for (int k = 128; k >= 1; k >>= 1) {
@@ -129,6 +230,18 @@ __global__ __launch_bounds__(256) void segment_sumsq_kernel(const float* __restr
     __syncthreads();
   }
   if (threadIdx.x == 0) out[seg] = red[0];
+}
+
+__global__ __launch_bounds__(256) void segment_sumsq_kernel(const float* __restrict__ flat,
+                                                            const int64_t* __restrict__ offsets,
+                                                            float* __restrict__ out) {
+  segment_sumsq_body(flat, offsets, out, nullptr);
+}
+
+__global__ __launch_bounds__(256) void segment_sumsq_flag_kernel(const float* __restrict__ flat,
+                                                                 const int64_t* __restrict__ offsets,
+                                                                 float* __restrict__ out, int32_t* __restrict__ flag) {
+  segment_sumsq_body(flat, offsets, out, flag);
 }
 
 }  // namespace
@@ -202,6 +315,88 @@ extern "C" int sg_segment_sumsq(const float* flat, const int64_t* offsets, float
                                 sg_stream_t st) {
   if (!flat || !offsets || !out || nseg < 1) return SG_EINVAL;
   hipLaunchKernelGGL(segment_sumsq_kernel, dim3(nseg), dim3(256), 0, sg_st(st), flat, offsets, out);
+  SG_LAUNCH_CHECK();
+  return SG_OK;
+}
+
+// ---- non-finite step guard ------------------------------------------------------------------------------------------
+static int clear_flag(int32_t* flag, sg_stream_t st) {
+  const hipError_t e = hipMemsetAsync(flag, 0, sizeof(int32_t), sg_st(st));
+  return e == hipSuccess ? SG_OK : (int)e;
+}
+
+extern "C" int sg_nonfinite_flag(const float* x, int64_t numel, int32_t* flag, int32_t accumulate, sg_stream_t st) {
+  if (!x || !flag || numel < 1) return SG_EINVAL;
+  if (!sg_aligned16(x)) return SG_EALIGN;
+  if (!accumulate) {
+    const int rc = clear_flag(flag, st);
+    if (rc != SG_OK) return rc;
+  }
+  int64_t blocks = (numel / 4 + 255) / 256;
+  if (blocks < 1) blocks = 1;
+  if (blocks > 2048) blocks = 2048;
+  hipLaunchKernelGGL(nonfinite_flag_kernel, dim3((unsigned)blocks), dim3(256), 0, sg_st(st), x, numel, flag);
+  SG_LAUNCH_CHECK();
+  return SG_OK;
+}
+
+extern "C" int sg_segment_sumsq_flag(const float* flat, const int64_t* offsets, float* out, int32_t nseg, int32_t* flag,
+                                     int32_t accumulate, sg_stream_t st) {
+  if (!flat || !offsets || !out || !flag || nseg < 1) return SG_EINVAL;
+  if (!accumulate) {
+    const int rc = clear_flag(flag, st);
+    if (rc != SG_OK) return rc;
+  }
+  hipLaunchKernelGGL(segment_sumsq_flag_kernel, dim3(nseg), dim3(256), 0, sg_st(st), flat, offsets, out, flag);
+  SG_LAUNCH_CHECK();
+  return SG_OK;
+}
+
+extern "C" int sg_guard_step(const int32_t* flag, int64_t* t, int64_t* counters, double lr, const double* lr_dev, float* lr_t,
+                             int32_t adam, double b1, double b2, sg_stream_t st) {
+  if (!flag || !t || !counters || !lr_t) return SG_EINVAL;
+  hipLaunchKernelGGL(guard_step_kernel, dim3(1), dim3(64), 0, sg_st(st), flag, t, counters, lr, lr_dev, lr_t, adam, b1, b2);
+  SG_LAUNCH_CHECK();
+  return SG_OK;
+}
+
+extern "C" int sg_adam_ema_guarded(float* p, const float* g, float* m, float* v, float* ema, int64_t numel, const float* lr_t,
+                                   const int32_t* skip, float b1, float b2, float eps, float gscale, float ema_decay,
+                                   sg_stream_t st) {
+  if (!p || !g || !m || !v || !lr_t || !skip || numel < 1) return SG_EINVAL;
+  if (!sg_aligned16(p) || !sg_aligned16(g) || !sg_aligned16(m) || !sg_aligned16(v) || (ema && !sg_aligned16(ema)))
+    return SG_EALIGN;
+  int64_t blocks = (numel / 4 + 255) / 256;
+  if (blocks < 1) blocks = 1;
+  if (blocks > 2048) blocks = 2048;
+  hipLaunchKernelGGL(adam_ema_guard_kernel, dim3((unsigned)blocks), dim3(256), 0, sg_st(st), p, g, m, v, ema, numel, lr_t,
+                     b1, b2, eps, gscale, ema_decay, skip);
+  SG_LAUNCH_CHECK();
+  return SG_OK;
+}
+
+extern "C" int sg_optim_step_guarded(int kind, float* p, const float* g, float* s1, float* s2, float* ema, int64_t numel,
+                                     const float* lr, const int32_t* skip, float h, float eps, int nesterov, float gscale,
+                                     float ema_decay, sg_stream_t st) {
+  if (!p || !g || !lr || !skip || numel < 1) return SG_EINVAL;
+  if (kind != SG_OPT_SGD && kind != SG_OPT_MOMENTUM && kind != SG_OPT_ADADELTA) return SG_EINVAL;
+  if ((kind != SG_OPT_SGD && !s1) || (kind == SG_OPT_ADADELTA && !s2)) return SG_EINVAL;
+  if (!sg_aligned16(p) || !sg_aligned16(g) || (s1 && !sg_aligned16(s1)) || (s2 && !sg_aligned16(s2)) ||
+      (ema && !sg_aligned16(ema)))
+    return SG_EALIGN;
+  int64_t blocks = (numel / 4 + 255) / 256;
+  if (blocks < 1) blocks = 1;
+  if (blocks > 2048) blocks = 2048;
+  const dim3 grid((unsigned)blocks), blk(256);
+  if (kind == SG_OPT_SGD)
+    hipLaunchKernelGGL(optim_step_guard_kernel<SG_OPT_SGD>, grid, blk, 0, sg_st(st), p, g, s1, s2, ema, numel, lr, h, eps,
+                       nesterov, gscale, ema_decay, skip);
+  else if (kind == SG_OPT_MOMENTUM)
+    hipLaunchKernelGGL(optim_step_guard_kernel<SG_OPT_MOMENTUM>, grid, blk, 0, sg_st(st), p, g, s1, s2, ema, numel, lr, h,
+                       eps, nesterov, gscale, ema_decay, skip);
+  else
+    hipLaunchKernelGGL(optim_step_guard_kernel<SG_OPT_ADADELTA>, grid, blk, 0, sg_st(st), p, g, s1, s2, ema, numel, lr, h,
+                       eps, nesterov, gscale, ema_decay, skip);
   SG_LAUNCH_CHECK();
   return SG_OK;
 }

@@ -1552,7 +1552,7 @@ class DevCoef(float):
         return o
 
     def ptr(self):
-        return C.c_void_p(self.buf.data_ptr() + 4 * self.idx)
+        return C.c_void_p(self.buf.data_ptr() + self.buf.element_size() * self.idx)
 
 
 class DevScalars:
@@ -1566,14 +1566,14 @@ class DevScalars:
     after that event (the host waits only if it is RING flushes ahead)."""
     RING = 8
 
-    def __init__(self, device, n=8):
+    def __init__(self, device, n=8, dtype=torch.float32):
         cuda = torch.device(device).type == 'cuda'
-        self._ring = [torch.zeros(n, dtype=torch.float32).pin_memory() if cuda else torch.zeros(n, dtype=torch.float32)
+        self._ring = [torch.zeros(n, dtype=dtype).pin_memory() if cuda else torch.zeros(n, dtype=dtype)
                       for _ in range(self.RING if cuda else 1)]
         self._events = [None] * len(self._ring)
         self._cur = 0
         self.host = self._ring[0]
-        self.dev = torch.zeros(n, dtype=torch.float32, device=device)
+        self.dev = torch.zeros(n, dtype=dtype, device=device)
         self.waits = 0            # times the host had to wait for a slot (tests)
 
     def set(self, idx, value):
@@ -1803,15 +1803,29 @@ def adam_step_size(lr, beta1, beta2, step):
     return lr * math.sqrt(1.0 - beta2 ** step) / (1.0 - beta1 ** step)
 
 
-def adam_ema_(p, g, m, v, ema, lr, beta1, beta2, step, eps=1e-8, gscale=1.0, ema_decay=0.99, lr_dev=None):
-    """In-place fused TF-Adam + EMA over flat f32 buffers.  lr_dev: a DevCoef holding lr_t on the
-    device (captured step): `lr` and `step` are then not used."""
+def _dev_ptr(x):
+    """Device address of a one-element step scalar: a DevCoef, or a tensor (its first element)."""
+    return x.ptr() if isinstance(x, DevCoef) else _ptr(x)
+
+
+def adam_ema_(p, g, m, v, ema, lr, beta1, beta2, step, eps=1e-8, gscale=1.0, ema_decay=0.99, lr_dev=None, skip=None):
+    """In-place fused TF-Adam + EMA over flat f32 buffers.  lr_dev: a DevCoef (or one-element f32
+    device tensor) holding lr_t on the device (captured step): `lr` and `step` are then not used.  skip: a one-element int32
+    device flag (non-finite step guard, sg_adam_ema_guarded): set, the launch is the EMA-only update; clear, it computes
+    what the lr_dev launch computes.  Needs lr_dev."""
     lib = _lib.load()
     _req_cuda(p, g, m, v, ema)
     if g is not None:
         mark_packs_stale()   # the kernel rewrites parameters behind torch's version counters
+    if skip is not None:
+        if lr_dev is None or g is None:
+            raise ValueError('adam_ema_: a guarded launch needs the gradient and the step size on the device (lr_dev)')
+        check(lib.sg_adam_ema_guarded(_ptr(p), _ptr(g), _ptr(m), _ptr(v), _ptr(ema), p.numel(), _dev_ptr(lr_dev), _ptr(skip),
+                                      float(beta1), float(beta2), float(eps), float(gscale), float(ema_decay), _stream()),
+              'sg_adam_ema_guarded')
+        return
     if lr_dev is not None and g is not None:
-        check(lib.sg_adam_ema_dev(_ptr(p), _ptr(g), _ptr(m), _ptr(v), _ptr(ema), p.numel(), lr_dev.ptr(), float(beta1),
+        check(lib.sg_adam_ema_dev(_ptr(p), _ptr(g), _ptr(m), _ptr(v), _ptr(ema), p.numel(), _dev_ptr(lr_dev), float(beta1),
                                   float(beta2), float(eps), float(gscale), float(ema_decay), _stream()), 'sg_adam_ema_dev')
         return
     lr_t = adam_step_size(lr, beta1, beta2, step) if g is not None else 0.0
@@ -1819,14 +1833,22 @@ def adam_ema_(p, g, m, v, ema, lr, beta1, beta2, step, eps=1e-8, gscale=1.0, ema
                           float(beta2), float(eps), float(gscale), float(ema_decay), _stream()), 'sg_adam_ema')
 
 
-def optim_step_(kind, p, g, s1, s2, ema, lr, h=0.0, eps=0.0, nesterov=False, gscale=1.0, ema_decay=0.99, lr_dev=None):
+def optim_step_(kind, p, g, s1, s2, ema, lr, h=0.0, eps=0.0, nesterov=False, gscale=1.0, ema_decay=0.99, lr_dev=None,
+                skip=None):
     """In-place fused SGD / Momentum / Adadelta (+ EMA) over flat f32 buffers (sg_optim_step; lr_dev: the learning rate as
-    a DevCoef on the device, captured step)."""
+    a DevCoef or one-element f32 tensor on the device, captured step; skip: the guard's int32 device flag, as in adam_ema_)."""
     lib = _lib.load()
     _req_cuda(p, g, s1, s2, ema)
     mark_packs_stale()      # the kernel rewrites parameters behind torch's version counters
+    if skip is not None:
+        if lr_dev is None:
+            raise ValueError('optim_step_: a guarded launch needs the step size on the device (lr_dev)')
+        check(lib.sg_optim_step_guarded(int(kind), _ptr(p), _ptr(g), _ptr(s1), _ptr(s2), _ptr(ema), p.numel(), _dev_ptr(lr_dev),
+                                        _ptr(skip), float(h), float(eps), 1 if nesterov else 0, float(gscale),
+                                        float(ema_decay), _stream()), 'sg_optim_step_guarded')
+        return
     if lr_dev is not None:
-        check(lib.sg_optim_step_dev(int(kind), _ptr(p), _ptr(g), _ptr(s1), _ptr(s2), _ptr(ema), p.numel(), lr_dev.ptr(), float(h),
+        check(lib.sg_optim_step_dev(int(kind), _ptr(p), _ptr(g), _ptr(s1), _ptr(s2), _ptr(ema), p.numel(), _dev_ptr(lr_dev), float(h),
                                     float(eps), 1 if nesterov else 0, float(gscale), float(ema_decay), _stream()),
               'sg_optim_step_dev')
         return
@@ -1835,8 +1857,37 @@ def optim_step_(kind, p, g, s1, s2, ema, lr, h=0.0, eps=0.0, nesterov=False, gsc
           'sg_optim_step')
 
 
-def segment_sumsq(flat, offsets_dev, nseg):
+def segment_sumsq(flat, offsets_dev, nseg, flag=None, accumulate=False):
+    """Per-segment sums of squares; flag (a one-element int32 device tensor): also the all-finite test of nonfinite_flag_
+    on the values read (sg_segment_sumsq_flag)."""
     lib = _lib.load()
     out = torch.empty(nseg, device=flat.device, dtype=torch.float32)
+    if flag is not None:
+        check(lib.sg_segment_sumsq_flag(_ptr(flat), _ptr(offsets_dev), _ptr(out), nseg, _ptr(flag), 1 if accumulate else 0,
+                                        _stream()), 'sg_segment_sumsq_flag')
+        return out
     check(lib.sg_segment_sumsq(_ptr(flat), _ptr(offsets_dev), _ptr(out), nseg, _stream()), 'sg_segment_sumsq')
     return out
+
+
+def nonfinite_flag_(flag, x, accumulate=False):
+    """flag (one-element int32 device tensor) = 1 if any entry of the flat f32 tensor x is NaN or +-Inf, else 0
+    (sg_nonfinite_flag; accumulate=True ORs into the flag instead of clearing it first).  No host sync."""
+    lib = _lib.load()
+    _req_cuda(flag, x)
+    if flag.dtype != torch.int32 or x.dtype != torch.float32 or not x.is_contiguous():
+        raise TypeError('nonfinite_flag_: an int32 flag and a contiguous float32 buffer')
+    check(lib.sg_nonfinite_flag(_ptr(x), x.numel(), _ptr(flag), 1 if accumulate else 0, _stream()), 'sg_nonfinite_flag')
+    return flag
+
+
+def guard_step_(flag, t, counters, lr, lr_t, adam=None, lr_dev=None):
+    """Bookkeeping of a guarded train op (sg_guard_step, one thread): flag clear -> t += 1 and lr_t = the step size at the
+    new t (adam=(beta1, beta2): Adam's bias-corrected lr, in double as adam_step_size; None: lr); flag set -> counters
+    [skipped, consecutive, longest run] advance.  t: int64 [1], counters: int64 [3], lr_t: f32 [1] (device tensors);
+    lr_dev: a float64 DevCoef read instead of `lr` (captured step)."""
+    lib = _lib.load()
+    _req_cuda(flag, t, counters, lr_t)
+    b1, b2 = adam if adam is not None else (0.0, 0.0)
+    check(lib.sg_guard_step(_ptr(flag), _ptr(t), _ptr(counters), float(lr), None if lr_dev is None else _dev_ptr(lr_dev),
+                            _ptr(lr_t), 1 if adam is not None else 0, float(b1), float(b2), _stream()), 'sg_guard_step')

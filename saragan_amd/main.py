@@ -66,6 +66,12 @@ def build_parser():
                    help='(not in the reference) always replay the training step as one hipGraph (SARAGAN_HIPGRAPH=1); by default a '
                         'phase is captured when its steps measure host-bound')
     p.add_argument('--no_hipgraph', default=False, action='store_true', help='(not in the reference) never capture: SARAGAN_HIPGRAPH=0')
+    p.add_argument('--skip_nonfinite_steps', default=False, action='store_true',
+                   help='(not in the reference) skip a network\'s update, on the device, when its gradient holds a NaN or Inf '
+                        '(saragan_amd.set_nonfinite_guard); the skip counts are printed on a line of their own at each log point')
+    p.add_argument('--max_consecutive_nonfinite', type=int, default=None,
+                   help='(not in the reference) with --skip_nonfinite_steps: stop with an error after N consecutive skipped steps '
+                        'of one network, without writing that phase\'s final checkpoint')
     p.add_argument('--ema_beta', type=float, default=0.99)
     p.add_argument('--noise_stddev', type=float, required=True)
     p.add_argument('--optimizer', type=none_or_str, choices=[None, 'Adam', 'SGD', 'Momentum', 'Adadelta'], default='Adam')
@@ -105,6 +111,11 @@ def build_parser():
 def finalize_args(args):
     """main.py:384-411 post-parse defaults: the discriminator inherits the generator's optimiser settings unless
     the --d_use_different_* switches are given; presets fill missing kernel/filter specs."""
+    if args.max_consecutive_nonfinite is not None:
+        if not args.skip_nonfinite_steps:
+            raise SystemExit('--max_consecutive_nonfinite needs --skip_nonfinite_steps')
+        if args.max_consecutive_nonfinite < 1:
+            raise SystemExit('--max_consecutive_nonfinite must be >= 1')
     if not args.d_use_different_optimizer:
         args.d_optimizer = args.optimizer
     if not args.d_use_different_beta1:

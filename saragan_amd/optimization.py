@@ -5,7 +5,12 @@ The reference builds TF1 graph ops and runs them with `sess.run(fetches, feed_di
 returns lightweight handles bound to a StepGraph; `Session.run([...handles...], feed_dict={real_image_input:
 batch})` executes ONE pass of the hot path for exactly the requested fetches: forward (4 discriminator passes,
 gradient penalty), backward, gradient all-reduce (if the optimizer is wrapped by
-parallel.DistributedOptimizer), optional global-norm clipping, and the fused TF-Adam(+EMA) kernel."""
+parallel.DistributedOptimizer), optional global-norm clipping, and the fused TF-Adam(+EMA) kernel.
+
+Not in the reference, off by default: the non-finite step guard (NonFiniteGuard; saragan_amd.set_nonfinite_guard,
+SARAGAN_NONFINITE_GUARD=1).  A train op whose reduced gradient holds a NaN / Inf leaves its parameters, optimiser slots and
+step count unchanged that step (the EMA update still runs), decided on the device so that a captured step stays a plain
+replay.  Measured cost on BASELINE configs[2]: +0.06 % of the step."""
 import importlib
 import math
 import os
@@ -29,6 +34,7 @@ class _Optimizer:
         self.t = 0
         self.state = {}          # prefix -> dict of flat state buffers
         self.distributed = None  # set by parallel.DistributedOptimizer
+        self.t_dev = None        # non-finite guard: the step count on the device (authoritative while a guard holds it)
 
     def lr_value(self):
         return float(self.lr.eval()) if isinstance(self.lr, ScalarVariable) else float(self.lr)
@@ -42,6 +48,24 @@ class _Optimizer:
         from device memory (functional.DevScalars); `apply(..., lr_dev=...)` then leaves the count alone."""
         self.t += 1
         return self.step_size()
+
+    def device_step_count(self, device):
+        """The guard's device copy of the step count (int64 [1]), made from the host count on first use."""
+        if self.t_dev is None:
+            self.t_dev = torch.tensor([self.t], dtype=torch.int64, device=device)
+        return self.t_dev
+
+    def sync_step_count(self):
+        """Host count <- device count (a sync: called only where the loop already waits for the device)."""
+        if self.t_dev is not None:
+            self.t = int(self.t_dev.item())
+        return self.t
+
+    def _guard_step(self, guard, adam=None):
+        """Guarded step: the bookkeeping launch (device t, step size, skip counters); returns the device step size."""
+        F.guard_step_(guard['flag'], self.t_dev, guard['counters'], guard['lr'], guard['lr_t'], adam=adam,
+                      lr_dev=guard['lr_dev'])
+        return guard['lr_t']
 
     def _slots(self, prefix, flat, names):
         st = self.state.get(prefix)
@@ -62,8 +86,15 @@ class AdamOptimizer(_Optimizer):
     def step_size(self):
         return F.adam_step_size(self.lr_value(), self.beta1, self.beta2, self.t)
 
-    def apply(self, prefix, flat, ranges, gscale, ema_flat, ema_decay, lr_dev=None):
+    def apply(self, prefix, flat, ranges, gscale, ema_flat, ema_decay, lr_dev=None, guard=None):
         st = self._slots(prefix, flat, ('m', 'v'))
+        if guard is not None:       # skipped on the device when the gradient is not finite; t counts applied updates only
+            lr_t = self._guard_step(guard, adam=(self.beta1, self.beta2))
+            for (o, n) in ranges:
+                F.adam_ema_(flat['param'][o:o + n], flat['grad'][o:o + n], st['m'][o:o + n], st['v'][o:o + n],
+                            None if ema_flat is None else ema_flat[o:o + n], 0.0, self.beta1, self.beta2, 0, self.epsilon,
+                            gscale, ema_decay, lr_dev=lr_t, skip=guard['flag'])
+            return
         if lr_dev is None:
             self.t += 1
         lr = self.lr_value()
@@ -80,9 +111,11 @@ class _FusedRule(_Optimizer):
     def _hyper(self):
         return dict(h=0.0, eps=0.0, nesterov=False)
 
-    def apply(self, prefix, flat, ranges, gscale, ema_flat, ema_decay, lr_dev=None):
+    def apply(self, prefix, flat, ranges, gscale, ema_flat, ema_decay, lr_dev=None, guard=None):
         st = self._slots(prefix, flat, self.SLOTS)
-        if lr_dev is None:
+        if guard is not None:
+            lr_dev = self._guard_step(guard)
+        elif lr_dev is None:
             self.t += 1
         lr = self.lr_value()
         for (o, n) in ranges:
@@ -90,7 +123,7 @@ class _FusedRule(_Optimizer):
             s2 = st[self.SLOTS[1]][o:o + n] if len(self.SLOTS) > 1 else None
             F.optim_step_(self.KIND, flat['param'][o:o + n], flat['grad'][o:o + n], s1, s2,
                           None if ema_flat is None else ema_flat[o:o + n], lr, gscale=gscale, ema_decay=ema_decay,
-                          lr_dev=lr_dev, **self._hyper())
+                          lr_dev=lr_dev, skip=None if guard is None else guard['flag'], **self._hyper())
 
 
 class GradientDescentOptimizer(_FusedRule):
@@ -187,6 +220,68 @@ def minimize_with_clipping(optimizer, loss, var_list, clipping):
             Fetch(graph, 'max_norm', tid))
 
 
+# ----------------------------------------------------------------------------------------------------
+# non-finite step guard (not in the reference)
+# ----------------------------------------------------------------------------------------------------
+class NonFiniteStepsError(RuntimeError):
+    """A network's train op was skipped --max_consecutive_nonfinite times in a row."""
+
+
+def nonfinite_guard_settings():
+    """(on, max_consecutive) as saragan_amd.set_nonfinite_guard / SARAGAN_NONFINITE_GUARD=1 left them: read when a StepGraph
+    is built."""
+    on = os.environ.get('SARAGAN_NONFINITE_GUARD', '') == '1'
+    mc = os.environ.get('SARAGAN_NONFINITE_MAX_CONSECUTIVE', '')
+    return on, (int(mc) if on and mc else None)
+
+
+class NonFiniteGuard:
+    """Device state of a StepGraph's guard.  Each train op checks its network's gradient after the data-parallel reduction
+    and before clipping (sg_nonfinite_flag, or fused into the clipping path's sg_segment_sumsq_flag); one bookkeeping thread
+    (sg_guard_step) then advances the optimiser's device step count and writes the step size -- or counts a skip -- and the
+    guarded update (sg_adam_ema_guarded / sg_optim_step_guarded) reads the flag: clear, exactly the unguarded update; set,
+    the EMA-only update.  Nothing is read back: the host sees the counters only where it syncs anyway."""
+    NETS = ('generator', 'discriminator')
+
+    def __init__(self, max_consecutive=None):
+        if max_consecutive is not None and int(max_consecutive) < 1:
+            raise ValueError('max_consecutive must be >= 1')
+        self.max_consecutive = None if max_consecutive is None else int(max_consecutive)
+        self.device = None
+
+    def prepare(self, graph, device):
+        """Allocates the flags, step sizes and counters and the optimisers' device step counts (outside any capture)."""
+        for tr in graph.trains:
+            tr['optimizer'].device_step_count(device)
+        if self.device is not None:
+            return
+        n = max(1, len(graph.trains))
+        self.flags = torch.zeros(n, dtype=torch.int32, device=device)
+        self.lr_t = torch.zeros(n, dtype=torch.float32, device=device)
+        self.counters = {net: torch.zeros(3, dtype=torch.int64, device=device) for net in self.NETS}
+        self.lr = F.DevScalars(device, n, dtype=torch.float64)     # base learning rates of a captured step (host-written)
+        self.device = device
+
+    def flag(self, tid):
+        return self.flags[tid:tid + 1]
+
+    def args(self, tid, net, optimizer, lr_dev=None):
+        """What a guarded optimizer.apply launches with.  lr_dev: the captured step's device copy of the base learning rate
+        (lr_coef); eager: the host value rides as a kernel argument."""
+        return dict(flag=self.flag(tid), lr_t=self.lr_t[tid:tid + 1], counters=self.counters[net],
+                    lr=optimizer.lr_value(), lr_dev=lr_dev)
+
+    def lr_coef(self, tid, value):
+        return self.lr.coef(tid, value)
+
+    def read(self):
+        """{net: (skipped, consecutive, longest run)}: one device-to-host copy (a sync)."""
+        if self.device is None:
+            return {net: (0, 0, 0) for net in self.NETS}
+        c = torch.stack([self.counters[net] for net in self.NETS]).cpu().tolist()
+        return {net: tuple(int(x) for x in row) for net, row in zip(self.NETS, c)}
+
+
 class StepGraph:
     """Everything optimize_step was told, plus the machinery to execute it."""
 
@@ -198,10 +293,53 @@ class StepGraph:
         self.flat_ready = False
         self.allreduce = None  # parallel.GradientAllReducer
         self.world = 1
+        on, max_consecutive = nonfinite_guard_settings()
+        self.guard = NonFiniteGuard(max_consecutive) if on else None
 
     def add_train(self, net, optimizer, names, clipping):
         self.trains.append(dict(net=net, optimizer=optimizer, names=names, clipping=bool(clipping)))
+        self._refuse_guard_with_adasum()
         return len(self.trains) - 1
+
+    # -- non-finite step guard ------------------------------------------------------------------------------------------
+    def configure_guard(self, on=True, max_consecutive=None):
+        """Turns the non-finite step guard on (or off) for this step graph, before its first step."""
+        if self.__dict__.get('_stepped'):
+            raise RuntimeError('configure_guard: call it before the first training step of the step graph')
+        self.guard = NonFiniteGuard(max_consecutive) if on else None
+        self._refuse_guard_with_adasum()
+
+    def _refuse_guard_with_adasum(self):
+        if self.guard is not None and any(getattr(t['optimizer'].distributed, 'delta_form', False) for t in self.trains):
+            # Adasum combines each rank's LOCAL weight delta: the ranks' gradients (and flags) differ, and a skipped rank's
+            # zero delta has no Adasum combination.  Refused rather than half-supported.
+            raise ValueError('the non-finite step guard does not support Adasum (--use_adasum): use the Average reduction '
+                             'or turn the guard off')
+
+    @property
+    def skipped_steps(self):
+        """{'generator': n, 'discriminator': n} skipped train ops (reads the device: a host sync)."""
+        rep = self.guard.read() if self.guard is not None else {n: (0, 0, 0) for n in NonFiniteGuard.NETS}
+        return {net: c[0] for net, c in rep.items()}
+
+    def guard_report(self):
+        """{net: (skipped, consecutive, longest run)}, and the optimisers' host step counts brought in line with the device
+        (a host sync: for the loop's existing sync points -- log line, checkpoint, phase end)."""
+        if self.guard is None:
+            return None
+        for tr in self.trains:
+            tr['optimizer'].sync_step_count()
+        return self.guard.read()
+
+    def check_nonfinite(self, global_step, report=None):
+        """Raises NonFiniteStepsError if a network's train op was skipped max_consecutive times in a row."""
+        if self.guard is None or self.guard.max_consecutive is None:
+            return
+        report = report or self.guard.read()
+        for net, (_, _, longest) in report.items():
+            if longest >= self.guard.max_consecutive:
+                raise NonFiniteStepsError(f'{net}: {longest} consecutive training steps had a non-finite gradient and were '
+                                          f'skipped (limit {self.guard.max_consecutive}) at global_step {global_step}')
 
     # -- flat buffers: frozen (previous-phase) variables first, new ones last -------------------------
     def _ensure_flat(self):
@@ -253,6 +391,10 @@ class StepGraph:
                 sample = c['generator'](z, alpha, c['phase'], c['base_shape'], activation=c['activation'],
                                         kernel_spec=c['kernel_spec'], filter_spec=c['filter_spec'], param=c['leakiness'])
             return [sample.detach() for _ in fetches]
+        self._stepped = True
+        if self.guard is not None:
+            self._refuse_guard_with_adasum()
+            self.guard.prepare(self, real.device)
         with use_store(self.store), torch.enable_grad():
             alpha = float(c['alpha'].eval()) if isinstance(c['alpha'], ScalarVariable) else float(c['alpha'])
             net_args = (c['latent_dim'], alpha, c['phase'], c['base_shape'], c['kernel_spec'], c['filter_spec'],
@@ -387,7 +529,8 @@ class StepGraph:
         alpha_class = 'mix' if 0.0 < alpha < 1.0 else float(alpha)
         norms = tuple(sorted(t for t in train_ids if ('max_norm', t) in self._wanted))
         dist_ids = tuple(t for t in train_ids if self.trains[t]['optimizer'].distributed is not None)
-        key = (tuple(train_ids), tuple(sorted(want_train)), norms, alpha_class, tuple(real.shape), str(compute_dtype()), strategy)
+        key = (tuple(train_ids), tuple(sorted(want_train)), norms, alpha_class, tuple(real.shape), str(compute_dtype()), strategy,
+               self.guard is not None)
         caps = self.__dict__.setdefault('_captures', {})
         ent = caps.get(key)
         if ent is None:
@@ -453,13 +596,20 @@ class StepGraph:
                 args[1] = sc.coef(0, alpha)
                 sc.set(1, 1.0 - alpha)
             ent['opt'] = []                                   # (train id, optimiser, scalar slot) of the captured applies
+            ent['glr'] = []                                   # guard: (train id, optimiser) whose base lr the host writes
             lr_dev = {}
             if not dist_ids:
                 for i, tid in enumerate(t for t in train_ids if t in want_train):
                     o = self.trains[tid]['optimizer']
-                    lr_dev[tid] = sc.coef(2 + i, o.next_step_size())
-                    ent['opt'].append((tid, o, 2 + i))
+                    if self.guard is not None:      # the step count and the step size are the device's (sg_guard_step)
+                        lr_dev[tid] = self.guard.lr_coef(tid, o.lr_value())
+                        ent['glr'].append((tid, o))
+                    else:
+                        lr_dev[tid] = sc.coef(2 + i, o.next_step_size())
+                        ent['opt'].append((tid, o, 2 + i))
             sc.flush()
+            if ent['glr']:
+                self.guard.lr.flush()
             ent['out'] = {}
             g = torch.cuda.CUDAGraph()
             L.set_random_source(ent['rnd'])
@@ -521,7 +671,7 @@ class StepGraph:
                 for _, o, _ in ent['opt']:
                     o.t -= 1
                 ent['decided'] = 'eager'
-                for k_ in ('real', 'rnd', 'scalars', 'opt', 'out', 'pend'):
+                for k_ in ('real', 'rnd', 'scalars', 'opt', 'glr', 'out', 'pend'):
                     ent.pop(k_, None)
                 # a kept filter-gradient workspace first made inside the failed capture had its zero-fill only RECORDED: it
                 # (and any other) goes, the next eager step makes clean ones
@@ -550,6 +700,10 @@ class StepGraph:
                 sc.set(slot, o.next_step_size())
             if alpha_class == 'mix' or ent['opt']:
                 sc.flush()
+            if ent['glr']:
+                for tid, o in ent['glr']:
+                    self.guard.lr.set(tid, o.lr_value())
+                self.guard.lr.flush()
         log = self.__dict__.get('_issue_log')          # tests: the host-side issue order of segments and bucket collectives
         if dist_ids and 'segments' in ent:
             # segment k, then the collectives of the network whose gradients it completed, then segment k + 1 (which they overlap)
@@ -645,14 +799,24 @@ class StepGraph:
         if info['dist'] is not None:
             info['dist'].finish()              # waits for the bucketed reductions
             gscale = info['dist'].grad_scale   # 1 / world after a SUM (the average is folded into the update kernel)
-        if tr['clipping'] or ('max_norm', tid) in self._wanted:
+        norms = tr['clipping'] or ('max_norm', tid) in self._wanted
+        guard = None
+        if apply and self.guard is not None:
+            # the reduced gradient, before clipping (an Inf would make the clip scale 0 and the products NaN); with norms
+            # wanted the test rides in their pass
+            guard = self.guard.args(tid, tr['net'], tr['optimizer'], lr_dev)
+            if not norms:
+                for j, (o, n) in enumerate(ranges):
+                    F.nonfinite_flag_(guard['flag'], flat['grad'][o:o + n], accumulate=j > 0)
+        if norms:
             if 'bounds' not in tr:
                 offs = flat['offsets']
                 b = torch.tensor([[offs[n][0], offs[n][0] + offs[n][1]] for n in names], dtype=torch.int64)
                 tr['bounds'] = b.reshape(-1).to(flat['grad'].device)
             # per-variable squared norms in ONE launch: offsets interleave [start_i, end_i); the odd segments
             # are the alignment padding between variables and are dropped
-            sq = F.segment_sumsq(flat['grad'], tr['bounds'], tr['bounds'].numel() - 1)[0::2] * (gscale * gscale)
+            sq = F.segment_sumsq(flat['grad'], tr['bounds'], tr['bounds'].numel() - 1,
+                                 flag=None if guard is None else guard['flag'])[0::2] * (gscale * gscale)
             if tr['clipping']:                 # tf.clip_by_global_norm(gradients, 1.0), optimization.py:66-67
                 scale = 1.0 / torch.clamp(torch.sqrt(sq.sum()), min=1.0)
                 out[('max_norm', tid)] = torch.sqrt(sq).max() * scale
@@ -675,7 +839,9 @@ class StepGraph:
         elif apply:
             ema_flat = self.ema.shadow_flat(info['prefix']) if self.ema is not None else None
             ema_decay = self.ema.decay if self.ema is not None else 0.0
-            if lr_dev is not None:
+            if guard is not None:
+                tr['optimizer'].apply(info['prefix'], flat, ranges, gscale, ema_flat, ema_decay, guard=guard)
+            elif lr_dev is not None:
                 tr['optimizer'].apply(info['prefix'], flat, ranges, gscale, ema_flat, ema_decay, lr_dev=lr_dev)
             else:
                 tr['optimizer'].apply(info['prefix'], flat, ranges, gscale, ema_flat, ema_decay)

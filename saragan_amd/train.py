@@ -134,6 +134,8 @@ def run_training(args, device=None, max_steps_per_phase=None, log_every=1):
         (train_gen, train_disc, gen_loss, disc_loss, gp_loss, gen_sample, _gg, g_variables, _dg, d_variables, _mg, _md,
          train_gen_freeze, _ggf, _gvf, _mgf, train_disc_freeze, _dgf, _dvf, _mdf) = tup
         graph = tup[0].graph
+        if getattr(args, 'skip_nonfinite_steps', False):      # (not in the reference) the non-finite step guard
+            graph.configure_guard(True, getattr(args, 'max_consecutive_nonfinite', None))
         var_list = [v.key for v in g_variables] + [v.key for v in d_variables]
         store.drop([k for k in list(store.vars) if k not in set(var_list)])
         if verbose:
@@ -168,6 +170,7 @@ def run_training(args, device=None, max_steps_per_phase=None, log_every=1):
             if not mixing_bool:
                 assert alpha.eval() == 0
             if global_step % args.checkpoint_every_nsteps < (batch_size * global_size) and local_step > 0:
+                graph.check_nonfinite(global_step)      # (a run that has been skipping stops before it writes)
                 if horovod:
                     parallel.broadcast_global_variables(store, 0)
                 if verbose:
@@ -209,6 +212,12 @@ def run_training(args, device=None, max_steps_per_phase=None, log_every=1):
             if want_log:
                 print_summary_to_stdout(global_step, int(in_phase_step), img_s, local_img_s, d_loss, g_loss,
                                         float(d_lr_val), float(g_lr_val), alpha)
+            if graph.guard is not None and (local_step // batch_size - 1) % log_every == 0:
+                # at the log point (every rank: the reduced gradients, hence the skips, are the same on all of them)
+                rep = graph.guard_report()
+                if want_log:
+                    print(f"Non-finite steps skipped: generator {rep['generator'][0]}, discriminator {rep['discriminator'][0]}")
+                graph.check_nonfinite(global_step, rep)
             if mixing_bool and (global_step >= ((phase - args.starting_phase) * (args.mixing_nimg + args.stabilizing_nimg)
                                                 + args.mixing_nimg)):
                 mixing_bool = False
@@ -223,6 +232,8 @@ def run_training(args, device=None, max_steps_per_phase=None, log_every=1):
         loader.close()
         gc.unfreeze()
         torch.cuda.synchronize()
+        if graph.guard is not None:      # before the phase's final checkpoint: a run that was skipping does not overwrite it
+            graph.check_nonfinite(global_step, graph.guard_report())
         stats[phase] = dict(img_s=imgs / max(1e-9, time.time() - t_phase), d_loss=d_loss, g_loss=g_loss,
                             batch_size=batch_size, steps=local_step // batch_size)
         # quirk Q5: the end-of-phase checkpoint holds the EMA weights of G AND D; the next phase starts from them
