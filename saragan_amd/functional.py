@@ -7,6 +7,7 @@ channels-last (torch.channels_last_3d == NDHWC); 2-D tensors [N, F] are NDHWC wi
 Each backward is itself built from these Functions, so second-order gradients (the gradient penalty of
 networks/loss.py:133-140 differentiates through D's data gradient) work.
 """
+import collections
 import contextlib
 import ctypes as C
 import math
@@ -70,6 +71,34 @@ def _ptr(t):
 
 
 # ---------------------------------------------------------------------------------------------------
+# diagnostic switches (SARAGAN_NO_X=1 in the environment; module globals, read where they are used: tests and tools set them)
+# ---------------------------------------------------------------------------------------------------
+def _switch(name):
+    return bool(int(os.environ.get('SARAGAN_' + name, '0')))
+
+
+_NO_PACK_BATCH = _switch('NO_PACK_BATCH')   # diagnostic: drop the images, one pack launch per layer and use
+# Sub-pixel form of upscale3d -> conv3d (sg_upconv3d_subpixel_fwd: one launch for all eight parity classes, 3.4x fewer
+# MFMAs than the 27-tap fused gather).  SARAGAN_NO_SUBPIXEL=1 keeps the gather kernels (A/B, tests).  (Round 2 had this form
+# as eight launches of the streamed kernel: 1.6 % slower per step than the gather, the phases too short to cover their halo
+# DMA and the stride-2 scatter writing half lines.)
+_NO_SUBPIXEL = _switch('NO_SUBPIXEL')
+_NO_CLEAN_WS = _switch('NO_CLEAN_WS')   # diagnostic: a fresh workspace + memset per weight gradient
+_NO_SIGN_WORDS = _switch('NO_SIGN_WORDS')   # diagnostic: activation-based masks only
+_NO_GRAD_DEST = _switch('NO_GRAD_DEST')   # diagnostic: gradients as tensors of their own, added by autograd
+_NO_PN_EPILOGUE = _switch('NO_PN_EPILOGUE')   # diagnostic: pixel-norm backward as its own pass
+_NO_PW_EPILOGUE = _switch('NO_PW_EPILOGUE')   # diagnostic: from_rgb's backward as its own pass over the gradient
+_NO_BACK_PREMASK = _switch('NO_BACK_PREMASK')   # diagnostic: always the separate mask pass
+_NO_RGB_FWD_EPILOGUE = _switch('NO_RGB_FWD_EPILOGUE')   # diagnostic: to_rgb's forward as its own pass over y
+_NO_RGB_FUSION = _switch('NO_RGB_FUSION')   # diagnostic: to_rgb's data gradient as a tensor
+_NO_RGB_WG_FUSION = _switch('NO_RGB_WG_FUSION')   # diagnostic: to_rgb's filter gradient as its own pass over y
+_NO_POOL3 = _switch('NO_POOL3')   # diagnostic: D x W means from the epilogue + the H pairs in a pass of their own
+_NO_POOL_FUSION = _switch('NO_POOL_FUSION')   # diagnostic: conv and downscale3d apart
+_NO_PLANES = _switch('NO_PLANES')   # diagnostic: the 64-channel gradient as one tensor
+_NO_GATHER_BWD = _switch('NO_GATHER_BWD')   # diagnostic: materialise the up-scaled gradient
+
+
+# ---------------------------------------------------------------------------------------------------
 # raw launches (no autograd)
 # ---------------------------------------------------------------------------------------------------
 def _shape(n, d, h, w, cin, cout, k, ups=False):
@@ -78,7 +107,6 @@ def _shape(n, d, h, w, cin, cout, k, ups=False):
 
 _PACK_CACHE = {}
 _PACK_STATE = {'stale': False}
-_NO_PACK_BATCH = bool(int(os.environ.get('SARAGAN_NO_PACK_BATCH', '0')))   # diagnostic: drop the images, one pack launch per layer and use
 PACK_STATS = {'single': 0, 'batches': 0, 'batched': 0}      # counters for the tests (host side only)
 
 
@@ -184,12 +212,7 @@ def sign_words(t):
     return out
 
 
-# Sub-pixel form of upscale3d -> conv3d (sg_upconv3d_subpixel_fwd: one launch for all eight parity classes, 3.4x fewer
-# MFMAs than the 27-tap fused gather).  SARAGAN_NO_SUBPIXEL=1 keeps the gather kernels (A/B, tests).  (Round 2 had this form
-# as eight launches of the streamed kernel: 1.6 % slower per step than the gather, the phases too short to cover their halo
-# DMA and the stride-2 scatter writing half lines.)
-_NO_SUBPIXEL = bool(int(os.environ.get('SARAGAN_NO_SUBPIXEL', '0')))
-_SUBPIX_CACHE = {}
+_SUBPIX_CACHE = {}      # summed sub-pixel weight images (see _NO_SUBPIXEL)
 
 
 def _subpixel_packed(w, coef, shp, dt, lib, st):
@@ -236,8 +259,14 @@ def _raw_upconv_subpixel(x, w, coef, bias, act, slope, pixel_norm, eps, want_sca
     return y, scale, signs
 
 
+# from_rgb's backward as an epilogue of the next layer's data gradient (raw_conv(pw_bwd=...), sg_conv_epilogue.pw_*): x the image,
+# wmat its [cout] f32 matrix (_rgb_matrix), want_dx whether the image gradient is formed, dw / db the f32 outputs (or None), coef
+PwBwd = collections.namedtuple('PwBwd', 'x wmat want_dx dw db coef')
+
+
 def raw_conv(x, w, coef, flip, ups=False, bias=None, act=False, slope=0.2, pixel_norm=False, eps=1e-8,
-             want_scale=False, mask_bits=None, mask_slope=0.0, want_signs=False, pool=False, pn_bwd=None, rgb=None, pw_bwd=None):
+             want_scale=False, mask_bits=None, mask_slope=0.0, want_signs=False, pool=False, pn_bwd=None, rgb=None, pw_bwd=None,
+             in_mask_bits=None, in_mask_slope=0.0, in_gain=1.0, x_plane_channels=0):
     """y = epilogue(conv3d(x, coef*w)) with w in DHWIO; `flip` selects the data-gradient weights.
     Returns (y, pixel-norm scale or None, sign words of y or None).  pool (sg_conv_epilogue.pool): 1 -- y is the
     2 x 1 x 2 (D x H x W) block mean of the output, [n,cout,d/2,h,w/2]; 2 -- the 1 x 2 x 2 block mean, [n,cout,d,h/2,w/2];
@@ -247,13 +276,23 @@ def raw_conv(x, w, coef, flip, ups=False, bias=None, act=False, slope=0.2, pixel
     None if no kernel does that for this layer.
     rgb = (matrix [cout] f32, bias tensor or None): to_rgb (one image channel) of the stored output in the epilogue
     (sg_conv_epilogue.rgb_*); returns (y, scale, signs, img), or None if the library has no such epilogue for this layer.
-    pw_bwd = dict(x=image, wmat=[cout] f32, want_dx, dw, db, coef): from_rgb's whole backward in the epilogue of this data
-    gradient (sg_conv_epilogue.pw_*; y is not written); returns the image gradient (or True when none was asked for), or None
-    if the library declines."""
+    pw_bwd (PwBwd): from_rgb's whole backward in the epilogue of this data gradient (sg_conv_epilogue.pw_*; y is not
+    written); returns the image gradient (or True when none was asked for), or None if the library declines.
+    in_mask_bits (with ups; sg_conv_epilogue.in_mask_*): the convolution reads in_gain * M * upscale3d(x), M the LeakyReLU
+    mask (in_mask_slope) of these sign words of the up-scaled tensor, formed while the tiles are staged.  x_plane_channels
+    (sg_conv_epilogue.x_plane_channels): x is [cin / pc, n, d, h, w, pc], the input channels as planes of pc channels.
+    Both ride on the library's two-pass path only: None where the layer has none, or the library declines."""
     lib = _lib.load()
     _req_cuda(x, w, bias)
-    x = ndhwc(x)
-    n, cx, d, h, wd = _dims(x)
+    if x_plane_channels:
+        if x.dim() != 6 or x.shape[5] != x_plane_channels or not x.is_contiguous():
+            raise ValueError('x_plane_channels: expected a contiguous [cin / pc, n, d, h, w, pc] tensor')
+        like = x[0].permute(0, 4, 1, 2, 3)       # one plane as [n,pc,d,h,w], channels last: the layout of what is allocated here
+        cx = x.shape[0] * x_plane_channels
+    else:
+        x = like = ndhwc(x)
+        cx = x.shape[1]
+    n, _, d, h, wd = _dims(like)
     if w.dim() == 2:
         w = w.reshape(1, 1, 1, *w.shape)
     kd, kh, kw, wi, wo = w.shape
@@ -270,12 +309,16 @@ def raw_conv(x, w, coef, flip, ups=False, bias=None, act=False, slope=0.2, pixel
     shp = _shape(n, d, h, wd, cin, cout, (kd, kh, kw), ups)
     dt = _dt(x)
     st = _stream()
+    ws_bytes = lib.sg_conv3d_fwd_workspace(C.byref(shp), dt)
+    if (in_mask_bits is not None or x_plane_channels) and not ws_bytes:
+        return None
+    _check_signs(in_mask_bits, n * d * h * wd, cin)
     wp = _packed(w, coef, flip, shp, dt, lib, st)
     pool = int(pool)
-    if pool and ({1: d | wd, 2: h | wd, 3: d | h | wd}[pool] & 1 or x.dim() != 5):
+    if pool and ({1: d | wd, 2: h | wd, 3: d | h | wd}[pool] & 1 or like.dim() != 5):
         return None
     y = None if pw_bwd is not None else \
-        _empty_like_shape(x, cout, {0: (d, h, wd), 1: (d // 2, h, wd // 2), 2: (d, h // 2, wd // 2), 3: (d // 2, h // 2, wd // 2)}[pool])
+        _empty_like_shape(like, cout, {0: (d, h, wd), 1: (d // 2, h, wd // 2), 2: (d, h // 2, wd // 2), 3: (d // 2, h // 2, wd // 2)}[pool])
     _check_signs(mask_bits, n * d * h * wd, cout)
     signs = _empty_signs(x.device, n, d, h, wd, cout) if want_signs else None
     scale = None
@@ -284,31 +327,33 @@ def raw_conv(x, w, coef, flip, ups=False, bias=None, act=False, slope=0.2, pixel
     b32 = bias.detach().contiguous().float() if bias is not None else None
     ep = ConvEpilogue(_ptr(b32), 1 if act else 0, float(slope), 1 if pixel_norm else 0, float(eps), _ptr(scale),
                       _ptr(mask_bits), float(mask_slope), _ptr(signs))
-    ep.pool = pool
+    ep.pool, ep.x_plane_channels = pool, x_plane_channels
+    if in_mask_bits is not None:
+        ep.in_mask_bits, ep.in_mask_slope, ep.in_gain = in_mask_bits.data_ptr(), float(in_mask_slope), float(in_gain)
     if pn_bwd is not None:
         pn_y, pn_scale = ndhwc(pn_bwd[0]), pn_bwd[1]
         if tuple(pn_y.shape) != tuple(y.shape) or pn_y.dtype != y.dtype or pn_scale.numel() != n * d * h * wd:
             raise ValueError('pn_bwd: y / scale do not match the convolution output')
         ep.pn_bwd_y, ep.pn_bwd_scale = pn_y.data_ptr(), pn_scale.data_ptr()
-    ws_bytes = lib.sg_conv3d_fwd_workspace(C.byref(shp), dt)
     if ws_bytes and not pool:      # scratch for the library's two-pass (K-split) path of this layer
         ws = torch.empty(ws_bytes, device=x.device, dtype=torch.uint8)
         ep.workspace, ep.workspace_bytes = ws.data_ptr(), ws_bytes
     img = dimg = None
     if rgb is not None:
-        img = _empty_like_shape(x, 1, (d, h, wd))
+        img = _empty_like_shape(like, 1, (d, h, wd))
         ep.rgb_w, ep.rgb_bias, ep.rgb_out = rgb[0].data_ptr(), (rgb[1].data_ptr() if rgb[1] is not None else None), img.data_ptr()
     if pw_bwd is not None:
         pws = lib.sg_conv3d_pw_epilogue_workspace()
         ws = torch.empty(pws, device=x.device, dtype=torch.uint8)
         ep.workspace, ep.workspace_bytes = ws.data_ptr(), pws
-        dimg = _empty_like_shape(x, 1, (d, h, wd)) if pw_bwd['want_dx'] else None
-        ep.pw_x, ep.pw_wmat, ep.pw_dx = pw_bwd['x'].data_ptr(), pw_bwd['wmat'].data_ptr(), (dimg.data_ptr() if dimg is not None else None)
-        ep.pw_dw = pw_bwd['dw'].data_ptr() if pw_bwd['dw'] is not None else None
-        ep.pw_dbias = pw_bwd['db'].data_ptr() if pw_bwd['db'] is not None else None
-        ep.pw_coef = float(pw_bwd['coef'])
+        dimg = _empty_like_shape(like, 1, (d, h, wd)) if pw_bwd.want_dx else None
+        ep.pw_x, ep.pw_wmat, ep.pw_dx = pw_bwd.x.data_ptr(), pw_bwd.wmat.data_ptr(), (dimg.data_ptr() if dimg is not None else None)
+        ep.pw_dw = pw_bwd.dw.data_ptr() if pw_bwd.dw is not None else None
+        ep.pw_dbias = pw_bwd.db.data_ptr() if pw_bwd.db is not None else None
+        ep.pw_coef = float(pw_bwd.coef)
     rc = lib.sg_conv3d_fwd(_ptr(x), _ptr(wp), _ptr(y), C.byref(shp), C.byref(ep), dt, st)
-    if (pool or pn_bwd is not None or rgb is not None or pw_bwd is not None) and rc == _lib.SG_EUNSUPPORTED:
+    optional = pool or pn_bwd is not None or rgb is not None or pw_bwd is not None or in_mask_bits is not None or x_plane_channels
+    if optional and rc == _lib.SG_EUNSUPPORTED:
         return None
     check(rc, 'sg_conv3d_fwd')
     if pw_bwd is not None:
@@ -320,7 +365,6 @@ def raw_conv(x, w, coef, flip, ups=False, bias=None, act=False, slope=0.2, pixel
 
 _CLEAN_WS = {}            # (device, workspace bytes) -> kept workspace, zero between calls (SG_WGRAD_CLEAN_WORKSPACE)
 _CLEAN_WS_DECLINED = set()   # shapes whose kernels do not leave the workspace clean (pointwise / small-channel paths)
-_NO_CLEAN_WS = bool(int(os.environ.get('SARAGAN_NO_CLEAN_WS', '0')))   # diagnostic: a fresh workspace + memset per weight gradient
 
 
 def clear_kept_workspaces():
@@ -379,13 +423,13 @@ def raw_wgrad(x, dy, k, coef, ups=False, want_db=False, w_ptr=0, b_ptr=0):
     shp = _shape(n, d, h, w, cin, cout, k, ups)
     acc = _grad_acc(w_ptr, (k[0], k[1], k[2], cin, cout))
     if acc is not None:       # a further contribution to a gradient that is in its slot already: added there, nothing returned
-        db = _f32_out(b_ptr, (cout,), x.device) if want_db else None      # (the bias gradient is written, not added)
+        outs = _GradOuts(x.device)
+        db = outs.take(b_ptr, (cout,), want_db)      # (the bias gradient is written, not added)
         rc = _wgrad_launch(lib, x, dy, None, 0.0, 1.0, acc, db, coef, True, shp, dt)
-        if rc != _lib.SG_EUNSUPPORTED:
+        if not outs.declined(rc):
             check(rc, 'sg_conv3d_wgrad_bias_ex (accumulate)')
             _note_accumulated(w_ptr)
             return None, db
-        _unclaim(b_ptr, db)
     dw = _f32_out(w_ptr, (k[0], k[1], k[2], cin, cout), x.device)
     db = _f32_out(b_ptr, (cout,), x.device) if want_db else None
     check(_wgrad_launch(lib, x, dy, None, 0.0, 1.0, dw, db, coef, False, shp, dt), 'sg_conv3d_wgrad_bias_ex')
@@ -416,7 +460,6 @@ def raw_bias_act_bwd(dy, y, slope, want_dx=True, want_db=False, b_ptr=0):
 # ---------------------------------------------------------------------------------------------------
 # autograd Functions
 # ---------------------------------------------------------------------------------------------------
-_NO_SIGN_WORDS = bool(int(os.environ.get('SARAGAN_NO_SIGN_WORDS', '0')))   # diagnostic: activation-based masks only
 _ZERO = {}
 
 
@@ -431,7 +474,6 @@ def _zero_scalar(like):
 
 _SKIP = {'ptrs': frozenset()}
 _GRAD_DEST = {}      # parameter data_ptr -> [f32 view of the step's flat gradient buffer, claimed]
-_NO_GRAD_DEST = bool(int(os.environ.get('SARAGAN_NO_GRAD_DEST', '0')))   # diagnostic: gradients as tensors of their own, added by autograd
 ACCUMULATED_IN_PLACE = set()   # data_ptr of the parameters whose slot took a later contribution in place during this backward
 GRAD_DEST_STATS = {'claimed': 0, 'accumulated': 0, 'adopted': 0, 'copied': 0, 'unreached': 0}   # counters for the tests (host side only)
 
@@ -507,6 +549,35 @@ def _f32_out(ptr, shape, device):
     return out if out is not None else torch.empty(shape, device=device, dtype=torch.float32)
 
 
+class _GradOuts:
+    """The f32 outputs of ONE launch that may decline (SG_EUNSUPPORTED: nothing was written, the caller takes another path).
+    take() hands each one out like _f32_out -- the parameter's slot when it is free, else a fresh tensor; declined(rc) / release()
+    frees exactly the slots that were claimed here (_unclaim says why none may be forgotten), fresh tensors are nobody's business."""
+
+    def __init__(self, device):
+        self.device, self.claimed = device, []
+
+    def take(self, ptr, shape, want=True):
+        if not want:
+            return None
+        out = _grad_out(ptr, shape)
+        if out is None:
+            return torch.empty(shape, device=self.device, dtype=torch.float32)
+        self.claimed.append((ptr, out))
+        return out
+
+    def release(self):
+        for ptr, out in self.claimed:
+            _unclaim(ptr, out)
+        self.claimed = []
+
+    def declined(self, rc):
+        if rc != _lib.SG_EUNSUPPORTED:
+            return False
+        self.release()
+        return True
+
+
 @contextlib.contextmanager
 def skip_param_grads(params):
     """Inside this context the backward Functions do not compute gradients of the given parameters.
@@ -537,8 +608,8 @@ class ActInfo:
         self.bits = None          # sign words of `a`, written by the producing conv's epilogue
         self.pn = None            # (y, scale) when the stage goes on through pixel_norm: y = pixel_norm(a); consumers that
         #                           registered as premask then apply the pixel-norm backward as well (_dgrad_into)
-        self.pw = None            # from_rgb (1x1x1 from one image channel): dict(x, w, coef, w_ptr, b_ptr, has_b, x_req) -- a consumer
-        #                           whose data-gradient kernel has the pw_* epilogue runs this layer's whole backward there ...
+        self.pw = None            # from_rgb (1x1x1 from one image channel): a PwStage -- a consumer whose data-gradient kernel
+        #                           has the pw_* epilogue runs this layer's whole backward there ...
         self.pw_result = None     # ... and leaves (gx, gw, gb) here for the layer's own backward to return (_dgrad_into)
         self.n_consumers = 0
         self.n_premask = 0
@@ -552,11 +623,13 @@ class ActInfo:
         return self.bits is not None and self.n_consumers > 0 and self.n_consumers == self.n_premask
 
 
+# from_rgb as its consumer's backward needs it (ActInfo.pw): the image x, the filter w and its runtime coefficient, the bias'
+# data_ptr (0: none), whether there is a bias, whether the image wants a gradient
+PwStage = collections.namedtuple('PwStage', 'x w coef b_ptr has_b x_req')
+
+
 def _masked_in(ctx_info):
     return ctx_info is not None and ctx_info.all_premask()
-
-
-_NO_PN_EPILOGUE = bool(int(os.environ.get('SARAGAN_NO_PN_EPILOGUE', '0')))   # diagnostic: pixel-norm backward as its own pass
 
 
 def pn_bwd_epilogue_available(prod_shape, kernel, fmaps, dtype):
@@ -591,9 +664,6 @@ def _dgrad_into(info, g, w, coef, flip):
     return _PnActBwd.apply(gy, info.pn[0], info.pn[1], info.bits, info.slope, False)[0]
 
 
-_NO_PW_EPILOGUE = bool(int(os.environ.get('SARAGAN_NO_PW_EPILOGUE', '0')))   # diagnostic: from_rgb's backward as its own pass over the gradient
-
-
 def _pw_fused_backward(info, g, w, coef, flip):
     """conv_1's data gradient with from_rgb's whole backward in its epilogue (sg_conv_epilogue.pw_*): the gradient of from_rgb's
     output -- 32 channels at full resolution, the largest tensor of the discriminator's backward, read once more by
@@ -601,24 +671,22 @@ def _pw_fused_backward(info, g, w, coef, flip):
     backward (which autograd runs next) finds (gx, gw, gb) in info.pw_result; what it is handed as `gy` is a stride-0 placeholder.
     None: the library has no such epilogue for this layer."""
     pw = info.pw
-    wr = pw['w']
+    wr = pw.w
     want_w = wr.data_ptr() not in _SKIP['ptrs']
-    want_b = pw['has_b'] and pw['b_ptr'] not in _SKIP['ptrs']
-    want_dx = bool(pw['x_req'])
+    want_b = pw.has_b and pw.b_ptr not in _SKIP['ptrs']
+    want_dx = bool(pw.x_req)
     if not (want_w or want_b or want_dx):
         return None
-    x_img = ndhwc(pw['x'])
+    x_img = ndhwc(pw.x)
     if x_img.dtype != g.dtype or x_img.shape[1] != 1:
         return None
-    cout = wr.shape[-1]
-    dw = _f32_out(wr.data_ptr(), tuple(wr.shape), g.device) if want_w else None
-    db = _f32_out(pw['b_ptr'], (cout,), g.device) if want_b else None
+    outs = _GradOuts(g.device)
+    dw = outs.take(wr.data_ptr(), tuple(wr.shape), want_w)
+    db = outs.take(pw.b_ptr, (wr.shape[-1],), want_b)
     res = raw_conv(g, w, coef, flip, mask_bits=info.bits, mask_slope=info.slope,
-                   pw_bwd=dict(x=x_img, wmat=_rgb_matrix(wr, pw['coef'], g.dtype, small_is_cin=True), want_dx=want_dx, dw=dw, db=db,
-                               coef=pw['coef']))
+                   pw_bwd=PwBwd(x_img, _rgb_matrix(wr, pw.coef, g.dtype, small_is_cin=True), want_dx, dw, db, pw.coef))
     if res is None:
-        _unclaim(wr.data_ptr(), dw)
-        _unclaim(pw['b_ptr'], db)
+        outs.release()
         return None
     info.pw_result = (res if want_dx else None, dw, db)
     n, c, d, h, wd = _dims(ndhwc(g))
@@ -648,9 +716,6 @@ class BackInfo:
         return self._decision
 
 
-_NO_BACK_PREMASK = bool(int(os.environ.get('SARAGAN_NO_BACK_PREMASK', '0')))   # diagnostic: always the separate mask pass
-
-
 def _note_consumer(t, premask=False):
     info = getattr(t, '_sg_back', None) if t is not None else None
     if info is not None and info._decision is None:
@@ -665,6 +730,36 @@ def _note_all(*args):
     for a in args:
         if isinstance(a, torch.Tensor):
             _note_consumer(a)
+
+
+def _conv_dgrad(g, w, coef, flip, ups=False, in_info=None, x_back=None):
+    """Gradient for the input x of a convolution (weights w; `flip` as raw_conv takes it for this gradient) given the
+    gradient g of its output.  ups: x went through the fused up-sample; x_back: x is a masked conv's output (BackInfo);
+    in_info: the ActInfo of the stage that produced x.  Through the Function forms: differentiable again, consumers counted."""
+    if ups:
+        return _upconv_dgrad(g, w, coef, flip)
+    if x_back is not None and x_back.all_premask():      # every consumer of x returns M * (its gradient): so does this one
+        return _Conv.apply(g, w, coef, flip, False, None, x_back.bits, x_back.slope)
+    if _masked_in(in_info):                              # the stage's backward in this kernel's epilogue
+        return _dgrad_into(in_info, g, w, coef, flip)
+    return _Conv.apply(g, w, coef, flip, False)
+
+
+def _conv_param_grads(x, g, w, coef, ups, want_w, want_db, b_ptr=0, gb=None):
+    """(gw, gb) of conv3d(x, coef * w) + b given the gradient g of its output.  gb: the bias gradient where an earlier pass
+    of the caller produced it; a missing one comes out of the filter-gradient launch, or, when the filter's is not wanted,
+    from a reduction of its own."""
+    db_here = want_db and gb is None
+    gw = None
+    if want_w:
+        k = tuple(w.shape[:3]) if w.dim() == 5 else (1, 1, 1)
+        gw, gb2 = _Wgrad.apply(x, g, k, coef, ups, db_here, w.data_ptr(), b_ptr)
+        gw = gw.reshape(w.shape) if gw is not None else None
+        if db_here:
+            gb = gb2
+    elif db_here:
+        _, gb = raw_bias_act_bwd(g, None, 0.0, want_dx=False, want_db=True, b_ptr=b_ptr)
+    return gw, (gb if want_db else None)
 
 
 class _Conv(torch.autograd.Function):
@@ -691,24 +786,13 @@ class _Conv(torch.autograd.Function):
             # already did so in the kernel that produced its share of gy
             gy, _ = _BiasActBwd.apply(gy, mask_bits, ctx.mask_slope, False)
         gx = gw = None
-        k = tuple(w.shape[:3]) if w.dim() == 5 else (1, 1, 1)
         if ctx.needs_input_grad[0]:
-            if ctx.ups:
-                gx = _upconv_dgrad(gy, w, ctx.coef, not ctx.flip)
-            elif ctx.x_back is not None and ctx.x_back.all_premask():
-                gx = _Conv.apply(gy, w, ctx.coef, not ctx.flip, False, None, ctx.x_back.bits, ctx.x_back.slope)
-            elif _masked_in(ctx.in_info):
-                gx = _dgrad_into(ctx.in_info, gy, w, ctx.coef, not ctx.flip)
-            else:
-                gx = _Conv.apply(gy, w, ctx.coef, not ctx.flip, False)
+            gx = _conv_dgrad(gy, w, ctx.coef, not ctx.flip, ctx.ups, ctx.in_info, ctx.x_back)
         if _wants(ctx, 1, w.data_ptr()):
-            if ctx.flip:
-                if ctx.ups:
-                    raise NotImplementedError
-                gw, _ = _Wgrad.apply(gy, x, k, ctx.coef, False, False, w.data_ptr())
-            else:
-                gw, _ = _Wgrad.apply(x, gy, k, ctx.coef, ctx.ups, False, w.data_ptr())
-            gw = gw.reshape(w.shape) if gw is not None else None
+            if ctx.flip and ctx.ups:
+                raise NotImplementedError
+            xs, gs = (gy, x) if ctx.flip else (x, gy)      # (a data-gradient conv: its input and its output gradient swap roles)
+            gw, _ = _conv_param_grads(xs, gs, w, ctx.coef, ctx.ups, True, False)
         return gx, gw, None, None, None, None, None, None
 
 
@@ -753,8 +837,7 @@ class _ConvBiasAct(torch.autograd.Function):
             out_info.pn = (y.detach(), scale) if pixel_norm else None
             if (act and not pixel_norm and not ups and signs is not None and w.dim() == 5 and tuple(w.shape[:4]) == (1, 1, 1, 1) and
                     x.dim() == 5 and not _NO_RGB_FUSION):      # from_rgb on one image channel (pgan/discriminator.py:9-12)
-                out_info.pw = dict(x=x.detach(), w=w, coef=coef, b_ptr=b.data_ptr() if b is not None else 0, has_b=b is not None,
-                                   x_req=x.requires_grad)
+                out_info.pw = PwStage(x.detach(), w, coef, b.data_ptr() if b is not None else 0, b is not None, x.requires_grad)
         ctx.save_for_backward(x, w, y if (pixel_norm or (act and signs is None)) else None, scale, signs)
         ctx.cfg = (coef, ups, act, slope, pixel_norm)
         ctx.has_b = b is not None
@@ -786,7 +869,7 @@ class _ConvBiasAct(torch.autograd.Function):
         premasked = act and not pixel_norm and _masked_in(ctx.out_info)   # every consumer already applied my mask
         if act and not premasked and not fused_pn_act:
             g, gb = _BiasActBwd.apply(g, signs if signs is not None else y.detach(), slope, want_db, ctx.b_ptr)
-        gx = gw = None
+        gx = None
         db_from_wgrad = want_db and gb is None
         if (ctx.needs_input_grad[0] and _wants(ctx, 1, w.data_ptr()) and not torch.is_grad_enabled() and not ups and
                 not _masked_in(ctx.in_info) and w.dim() == 5 and x.dim() == 5 and tuple(w.shape[:3]) == (1, 1, 1) and w.shape[3] <= 4 and
@@ -796,26 +879,9 @@ class _ConvBiasAct(torch.autograd.Function):
                 gx, gw, gb2 = res
                 return gx, gw, ((gb2 if db_from_wgrad else gb) if want_db else None), None, None, None, None, None, None, None, None
         if ctx.needs_input_grad[0]:
-            if ups:
-                gx = _upconv_dgrad(g, w, coef, True)
-            elif _masked_in(ctx.in_info):
-                gx = _dgrad_into(ctx.in_info, g, w, coef, True)
-            else:
-                gx = _Conv.apply(g, w, coef, True, False)
-        if _wants(ctx, 1, w.data_ptr()):
-            k = tuple(w.shape[:3]) if w.dim() == 5 else (1, 1, 1)
-            gw, gb2 = _Wgrad.apply(x, g, k, coef, ups, db_from_wgrad, w.data_ptr(), ctx.b_ptr)
-            gw = gw.reshape(w.shape) if gw is not None else None
-            if db_from_wgrad:
-                gb = gb2
-        elif db_from_wgrad:
-            _, gb = raw_bias_act_bwd(g, None, 0.0, want_dx=False, want_db=True, b_ptr=ctx.b_ptr)
-        return gx, gw, (gb if want_db else None), None, None, None, None, None, None, None, None
-
-
-_NO_RGB_FWD_EPILOGUE = bool(int(os.environ.get('SARAGAN_NO_RGB_FWD_EPILOGUE', '0')))   # diagnostic: to_rgb's forward as its own pass over y
-_NO_RGB_FUSION = bool(int(os.environ.get('SARAGAN_NO_RGB_FUSION', '0')))   # diagnostic: to_rgb's data gradient as a tensor
-_NO_RGB_WG_FUSION = bool(int(os.environ.get('SARAGAN_NO_RGB_WG_FUSION', '0')))   # diagnostic: to_rgb's filter gradient as its own pass over y
+            gx = _conv_dgrad(g, w, coef, True, ups, ctx.in_info)
+        gw, gb = _conv_param_grads(x, g, w, coef, ups, _wants(ctx, 1, w.data_ptr()), want_db, ctx.b_ptr, gb)
+        return gx, gw, gb, None, None, None, None, None, None, None, None
 
 
 def _rgb_matrix(w_rgb, coef, dtype, small_is_cin=False):
@@ -845,14 +911,13 @@ def _pw_backward(x, dy, w, coef, want_db, b_ptr=0):
     dt = _dt(x)
     ws_bytes = lib.sg_conv3d_wgrad_workspace(C.byref(shp), dt)
     ws = torch.empty(ws_bytes, device=x.device, dtype=torch.uint8)
-    dw = _f32_out(w.data_ptr(), (1, 1, 1, cin, cout), x.device)
-    db = _f32_out(b_ptr, (cout,), x.device) if want_db else None
+    outs = _GradOuts(x.device)
+    dw = outs.take(w.data_ptr(), (1, 1, 1, cin, cout))
+    db = outs.take(b_ptr, (cout,), want_db)
     gx = torch.empty_like(x)
     rc = lib.sg_conv3d_pw_bwd(_ptr(x), _ptr(dy), _ptr(_rgb_matrix(w, coef, x.dtype, True)), _ptr(dw), _ptr(db), _ptr(gx),
                               float(coef), _ptr(ws), ws_bytes, C.byref(shp), dt, _stream())
-    if rc == _lib.SG_EUNSUPPORTED:
-        _unclaim(w.data_ptr(), dw)
-        _unclaim(b_ptr, db)
+    if outs.declined(rc):
         return None
     check(rc, 'sg_conv3d_pw_bwd')
     return gx, dw.reshape(w.shape), db
@@ -915,37 +980,31 @@ class _ConvPnActToRgb(torch.autograd.Function):
             # to_rgb's data gradient AND its own filter / bias gradient inside the pixel-norm / LeakyReLU backward pass: all three
             # need only y and the image gradient, which that pass reads anyway (a separate filter-gradient pass re-read y: 1.07 GB)
             g = torch.empty_like(y)
-            gb = _f32_out(ctx.ptrs[1], (c,), y.device) if want_db else None
-            gw_rgb = _f32_out(ctx.ptrs[2], tuple(w_rgb.shape), y.device) if want_w_rgb else None
-            gb_rgb = _f32_out(ctx.ptrs[3], (cs,), y.device) if want_db_rgb else None
+            outs = _GradOuts(y.device)
+            gb = outs.take(ctx.ptrs[1], (c,), want_db)
+            gw_rgb = outs.take(ctx.ptrs[2], tuple(w_rgb.shape), want_w_rgb)
+            gb_rgb = outs.take(ctx.ptrs[3], (cs,), want_db_rgb)
             ws_bytes = lib.sg_pixel_norm_act_bwd_pw_wg_workspace(c, cs)
             ws = torch.empty(ws_bytes, device=y.device, dtype=torch.uint8)
             rc = lib.sg_pixel_norm_act_bwd_pw_wg(_ptr(g_img), cs, _ptr(_rgb_matrix(w_rgb, coef_rgb, y.dtype)), _ptr(y), _ptr(scale), _ptr(signs),
                                                  float(slope), _ptr(g), _ptr(gb), _ptr(gw_rgb), _ptr(gb_rgb), float(coef_rgb), _ptr(ws), ws_bytes,
                                                  nvox, c, _dt(y), _stream())
-            if rc == _lib.SG_EUNSUPPORTED:
-                _unclaim(ctx.ptrs[1], gb)
-                _unclaim(ctx.ptrs[2], gw_rgb)
-                _unclaim(ctx.ptrs[3], gb_rgb)
+            if outs.declined(rc):
                 g = gb = gw_rgb = gb_rgb = None
             else:
                 check(rc, 'sg_pixel_norm_act_bwd_pw_wg')
                 done_rgb = True
         if g_img is not None and not done_rgb:
-            if want_w_rgb:
-                gw_rgb, gb_rgb = raw_wgrad(y, g_img, (1, 1, 1), coef_rgb, False, want_db_rgb, ctx.ptrs[2], ctx.ptrs[3])
-                gw_rgb = gw_rgb.reshape(w_rgb.shape) if gw_rgb is not None else None
-            elif want_db_rgb:
-                _, gb_rgb = raw_bias_act_bwd(g_img, None, 0.0, want_dx=False, want_db=True, b_ptr=ctx.ptrs[3])
+            gw_rgb, gb_rgb = _conv_param_grads(y, g_img, w_rgb, coef_rgb, False, want_w_rgb, want_db_rgb, ctx.ptrs[3])
         if fuse and g is None:
             g = torch.empty_like(y)
-            gb = _f32_out(ctx.ptrs[1], (c,), y.device) if want_db else None
+            outs = _GradOuts(y.device)
+            gb = outs.take(ctx.ptrs[1], (c,), want_db)
             ws = torch.empty(lib.sg_bias_act_bwd_workspace(c), device=y.device, dtype=torch.uint8) if want_db else None
             rc = lib.sg_pixel_norm_act_bwd_pw(_ptr(g_img), cs, _ptr(_rgb_matrix(w_rgb, coef_rgb, y.dtype)), _ptr(y), _ptr(scale),
                                               _ptr(signs), float(slope), _ptr(g), _ptr(gb), _ptr(ws), nvox, c, _dt(y), _stream())
-            if rc == _lib.SG_EUNSUPPORTED:
-                g = None
-                _unclaim(ctx.ptrs[1], gb)
+            if outs.declined(rc):
+                g = gb = None
             else:
                 check(rc, 'sg_pixel_norm_act_bwd_pw')
         if g is None:       # y has other consumers (or the library declined): the gradient for y as a tensor
@@ -955,23 +1014,9 @@ class _ConvPnActToRgb(torch.autograd.Function):
             g, gb = _PnActBwd.apply(gy, y, scale, signs, slope, want_db, ctx.ptrs[1])
             if not want_db:
                 gb = None
-        gx = gw = None
-        if ctx.needs_input_grad[0]:
-            if ups:
-                gx = _upconv_dgrad(g, w, coef, True)
-            elif _masked_in(ctx.in_info):
-                gx = _dgrad_into(ctx.in_info, g, w, coef, True)
-            else:
-                gx = raw_conv(g, w, coef, True, False)[0]
-        if _wants(ctx, 1, ctx.ptrs[0]):
-            k = tuple(w.shape[:3]) if w.dim() == 5 else (1, 1, 1)
-            gw, _ = raw_wgrad(x, g, k, coef, ups, False, ctx.ptrs[0])
-            gw = gw.reshape(w.shape) if gw is not None else None
+        gx = _conv_dgrad(g, w, coef, True, ups, ctx.in_info) if ctx.needs_input_grad[0] else None
+        gw, _ = _conv_param_grads(x, g, w, coef, ups, _wants(ctx, 1, ctx.ptrs[0]), False)
         return gx, gw, gb, None, None, None, None, None, gw_rgb, gb_rgb, None
-
-
-_NO_POOL3 = bool(int(os.environ.get('SARAGAN_NO_POOL3', '0')))   # diagnostic: D x W means from the epilogue + the H pairs in a pass of their own
-_NO_POOL_FUSION = bool(int(os.environ.get('SARAGAN_NO_POOL_FUSION', '0')))   # diagnostic: conv and downscale3d apart
 
 
 class _ConvBiasActPool(torch.autograd.Function):
@@ -1032,53 +1077,20 @@ class _ConvBiasActPool(torch.autograd.Function):
             except _GatherDeclined:
                 pass
         g = _Up.apply(gy, 0.125, signs, slope, (2, 2, 2))      # d(downscale3d) * LeakyReLU mask, full resolution
-        gx = gw = gb = None
-        if ctx.needs_input_grad[0]:
-            if _masked_in(ctx.in_info):
-                gx = _dgrad_into(ctx.in_info, g, w, coef, True)
-            else:
-                gx = _Conv.apply(g, w, coef, True, False)
-        if _wants(ctx, 1, w.data_ptr()):
-            gw, gb = _Wgrad.apply(x, g, tuple(w.shape[:3]), coef, False, want_db, w.data_ptr(), ctx.b_ptr)
-            gw = gw.reshape(w.shape) if gw is not None else None
-        elif want_db:
-            _, gb = raw_bias_act_bwd(g, None, 0.0, want_dx=False, want_db=True, b_ptr=ctx.b_ptr)
-        return gx, gw, (gb if want_db else None), None, None, None
-
-
-_NO_PLANES = bool(int(os.environ.get('SARAGAN_NO_PLANES', '0')))   # diagnostic: the 64-channel gradient as one tensor
-_NO_GATHER_BWD = bool(int(os.environ.get('SARAGAN_NO_GATHER_BWD', '0')))   # diagnostic: materialise the up-scaled gradient
+        gx = _conv_dgrad(g, w, coef, True, False, ctx.in_info) if ctx.needs_input_grad[0] else None
+        gw, gb = _conv_param_grads(x, g, w, coef, False, _wants(ctx, 1, w.data_ptr()), want_db, ctx.b_ptr)
+        return gx, gw, gb, None, None, None
 
 
 class _GatherDeclined(Exception):
     """The library has no fused-gather tile for this launch (the caller takes the materialised path)."""
 
 
-def _gather_dgrad_launch(gy, w, signs, slope, coef, mask_bits, mask_slope):
-    """gx = [mask] conv'(M * upscale3d(gy) / 8) through sg_conv_epilogue.in_mask_bits (the two-pass 64 -> 32 path)."""
-    lib = _lib.load()
-    gy = ndhwc(gy)
-    n, cout, dc, hc, wc = _dims(gy)
-    d, h, wd = 2 * dc, 2 * hc, 2 * wc
-    dt, st = _dt(gy), _stream()
-    shp = _shape(n, d, h, wd, 64, 32, (3, 3, 3), True)
-    ws_bytes = lib.sg_conv3d_fwd_workspace(C.byref(shp), dt)
-    if not ws_bytes:
-        raise _GatherDeclined()
-    _check_signs(signs, n * d * h * wd, 64)
-    wp = _packed(w, coef, True, shp, dt, lib, st)
-    gx = _empty_like_shape(gy, 32, (d, h, wd))
-    ep = ConvEpilogue(None, 0, 0.0, 0, 1e-8, None, _ptr(mask_bits), float(mask_slope) if mask_bits is not None else 0.0, None)
-    if mask_bits is not None:
-        _check_signs(mask_bits, n * d * h * wd, 32)
-    ws = torch.empty(ws_bytes, device=gy.device, dtype=torch.uint8)
-    ep.workspace, ep.workspace_bytes = ws.data_ptr(), ws_bytes
-    ep.in_mask_bits, ep.in_mask_slope, ep.in_gain = signs.data_ptr(), float(slope), 0.125
-    rc = lib.sg_conv3d_fwd(_ptr(gy), _ptr(wp), _ptr(gx), C.byref(shp), C.byref(ep), dt, st)
-    if rc == _lib.SG_EUNSUPPORTED:
-        raise _GatherDeclined()
-    check(rc, 'sg_conv3d_fwd (masked gather)')
-    return gx
+def _gather_dgrad(gy, w, signs, slope, coef, mask_bits, mask_slope):
+    """gx = [mask] conv'(M * upscale3d(gy) / 8) through sg_conv_epilogue.in_mask_bits (the two-pass 64 -> 32 path), or None."""
+    res = raw_conv(gy, w, coef, True, True, slope=0.0, mask_bits=mask_bits, mask_slope=mask_slope if mask_bits is not None else 0.0,
+                   in_mask_bits=signs, in_mask_slope=slope, in_gain=0.125)
+    return res[0] if res is not None else None
 
 
 class _PooledDgradGather(torch.autograd.Function):
@@ -1091,7 +1103,9 @@ class _PooledDgradGather(torch.autograd.Function):
     @staticmethod
     def forward(ctx, gy, w, signs, slope, coef, mask_bits, mask_slope):
         _note_all(gy)
-        gx = _gather_dgrad_launch(gy, w, signs, slope, coef, mask_bits, mask_slope)
+        gx = _gather_dgrad(gy, w, signs, slope, coef, mask_bits, mask_slope)
+        if gx is None:
+            raise _GatherDeclined()
         ctx.save_for_backward(gy, w, signs, mask_bits)
         ctx.cfg = (float(slope), float(coef), float(mask_slope))
         ctx.out_back = None
@@ -1136,10 +1150,10 @@ class _PooledDgradGather(torch.autograd.Function):
                 check(rc, 'sg_conv3d_wgrad_bias_ex (gathered dy, accumulate)')
                 _note_accumulated(w.data_ptr())
                 return g_gy, None, None, None, None, None, None
-            dw = _f32_out(w.data_ptr(), (3, 3, 3, 32, 64), ggx.device)
+            outs = _GradOuts(ggx.device)
+            dw = outs.take(w.data_ptr(), (3, 3, 3, 32, 64))
             rc = _wgrad_launch(lib, ggx_, gy_, signs, slope, 0.125, dw, None, coef, False, shp, dt)
-            if rc == _lib.SG_EUNSUPPORTED:      # the materialised pair, as the plain path computes it
-                _unclaim(w.data_ptr(), dw)
+            if outs.declined(rc):      # the materialised pair, as the plain path computes it
                 g_full = _Up.apply(gy_, 0.125, signs, slope, (2, 2, 2))
                 dw, _ = raw_wgrad(ggx_, g_full, (3, 3, 3), coef, False, False, w.data_ptr())
             else:
@@ -1161,39 +1175,21 @@ def _pooled_backward_gather(gy, x, w, signs, coef, slope, in_info, want_gx, want
     gy, x = ndhwc(gy), ndhwc(x)
     n, cout, dc, hc, wc = _dims(gy)
     d, h, wd = 2 * dc, 2 * hc, 2 * wc
-    dt, st = _dt(gy), _stream()
-    k = (3, 3, 3)
     _check_signs(signs, n * d * h * wd, 64)
     gx = gw = gb = None
     if want_gx:
-        shp = _shape(n, d, h, wd, 64, 32, k, True)
-        ws_bytes = lib.sg_conv3d_fwd_workspace(C.byref(shp), dt)
-        if not ws_bytes:
-            return None
-        wp = _packed(w, coef, True, shp, dt, lib, st)
-        gx = _empty_like_shape(gy, 32, (d, h, wd))
         masked = _masked_in(in_info)
-        ep = ConvEpilogue(None, 0, 0.0, 0, 1e-8, None, _ptr(in_info.bits) if masked else None,
-                          float(in_info.slope) if masked else 0.0, None)
-        if masked:
-            _check_signs(in_info.bits, n * d * h * wd, 32)
-        ws = torch.empty(ws_bytes, device=gy.device, dtype=torch.uint8)
-        ep.workspace, ep.workspace_bytes = ws.data_ptr(), ws_bytes
-        ep.in_mask_bits, ep.in_mask_slope, ep.in_gain = signs.data_ptr(), float(slope), 0.125
-        rc = lib.sg_conv3d_fwd(_ptr(gy), _ptr(wp), _ptr(gx), C.byref(shp), C.byref(ep), dt, st)
-        if rc == _lib.SG_EUNSUPPORTED:
+        gx = _gather_dgrad(gy, w, signs, slope, coef, in_info.bits if masked else None, in_info.slope if masked else 0.0)
+        if gx is None:
             return None
-        check(rc, 'sg_conv3d_fwd (masked gather)')
     if want_gw or want_db:
-        shp = _shape(n, d, h, wd, 32, 64, k, False)
+        shp = _shape(n, d, h, wd, 32, 64, (3, 3, 3), False)
+        outs = _GradOuts(gy.device)
         acc = _grad_acc(w.data_ptr(), (3, 3, 3, 32, 64)) if want_gw else None
-        dw = acc if acc is not None else _f32_out(w.data_ptr() if want_gw else 0, (3, 3, 3, 32, 64), gy.device)
-        gb = _f32_out(b_ptr, (64,), gy.device) if want_db else None
-        rc = _wgrad_launch(lib, x, gy, signs, slope, 0.125, dw, gb, coef, acc is not None, shp, dt)
-        if rc == _lib.SG_EUNSUPPORTED:
-            if acc is None:
-                _unclaim(w.data_ptr(), dw)
-            _unclaim(b_ptr, gb)
+        dw = acc if acc is not None else outs.take(w.data_ptr() if want_gw else 0, (3, 3, 3, 32, 64))
+        gb = outs.take(b_ptr, (64,), want_db)
+        rc = _wgrad_launch(lib, x, gy, signs, slope, 0.125, dw, gb, coef, acc is not None, shp, _dt(gy))
+        if outs.declined(rc):
             return None
         check(rc, 'sg_conv3d_wgrad_bias_ex (gathered dy)')
         if acc is not None:
@@ -1230,19 +1226,12 @@ def _pooled_backward_planes(gy, x, w, signs, coef, slope, in_info, want_gx, want
     check(rc, 'sg_upscale_nn_planes')
     gx = gw = gb = None
     if want_gx:
-        wp = _packed(w, coef, True, shp, dt, lib, st)
-        gx = _empty_like_shape(gy, 32, (d, h, wd))
         masked = _masked_in(in_info)
-        ep = ConvEpilogue(None, 0, 0.0, 0, 1e-8, None, _ptr(in_info.bits) if masked else None,
-                          float(in_info.slope) if masked else 0.0, None)
-        if masked:
-            _check_signs(in_info.bits, n * d * h * wd, 32)
-        ws = torch.empty(ws_bytes, device=gy.device, dtype=torch.uint8)
-        ep.workspace, ep.workspace_bytes, ep.x_plane_channels = ws.data_ptr(), ws_bytes, 32
-        rc = lib.sg_conv3d_fwd(_ptr(planes), _ptr(wp), _ptr(gx), C.byref(shp), C.byref(ep), dt, st)
-        if rc == _lib.SG_EUNSUPPORTED:
+        res = raw_conv(planes, w, coef, True, False, slope=0.0, mask_bits=in_info.bits if masked else None,
+                       mask_slope=in_info.slope if masked else 0.0, x_plane_channels=32)
+        if res is None:
             return None
-        check(rc, 'sg_conv3d_fwd (planes)')
+        gx = res[0]
     if want_gw or want_db:
         halves = [planes[i].permute(0, 4, 1, 2, 3) for i in range(2)]       # [n,32,d,h,w], channels last
         if want_gw:

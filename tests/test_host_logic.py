@@ -291,6 +291,54 @@ def test_gradient_destination_registry():
     assert not F._GRAD_DEST
 
 
+def test_grad_outs_release_exactly_what_they_claimed():
+    """functional._GradOuts (host logic only): the outputs of one launch that may decline.  Declined: every slot handed out
+    here is free again; accepted: they stay claimed; an output that was a fresh tensor (slot already claimed, or no parameter
+    behind it) is not touched by the release."""
+    import torch
+    from saragan_amd import _lib
+    from saragan_amd import functional as F
+    flat = torch.zeros(64)
+    w = torch.nn.Parameter(torch.ones(2, 3))
+    b = torch.nn.Parameter(torch.ones(3))
+    wp, bp = w.data_ptr(), b.data_ptr()
+    slots = {wp: flat[8:14].view(2, 3), bp: flat[16:19]}
+    cpu = torch.device('cpu')
+    with F.grads_into(slots), torch.no_grad():
+        before = F.GRAD_DEST_STATS['claimed']
+        # declined
+        outs = F._GradOuts(cpu)
+        dw, db = outs.take(wp, (2, 3)), outs.take(bp, (3,))
+        assert outs.take(bp, (3,), False) is None                         # not wanted: nothing handed out
+        assert dw.data_ptr() == slots[wp].data_ptr() and db.data_ptr() == slots[bp].data_ptr()
+        assert F.GRAD_DEST_STATS['claimed'] == before + 2
+        assert not outs.declined(0) and F.GRAD_DEST_STATS['claimed'] == before + 2
+        assert outs.declined(_lib.SG_EUNSUPPORTED)
+        assert F.GRAD_DEST_STATS['claimed'] == before
+        assert F._grad_acc(wp, (2, 3)) is None and F._grad_acc(bp, (3,)) is None
+        assert F._grad_out(wp, (2, 3)) is not None and F._grad_out(bp, (3,)) is not None      # free again (and now taken)
+        F._unclaim(wp, slots[wp])
+        F._unclaim(bp, slots[bp])
+        assert F.GRAD_DEST_STATS['claimed'] == before
+        # accepted
+        outs = F._GradOuts(cpu)
+        dw, db = outs.take(wp, (2, 3)), outs.take(bp, (3,))
+        assert not outs.declined(0)
+        assert F.GRAD_DEST_STATS['claimed'] == before + 2
+        assert F._grad_acc(wp, (2, 3)) is not None and F._grad_acc(bp, (3,)) is not None
+        assert F._grad_out(wp, (2, 3)) is None and F._grad_out(bp, (3,)) is None
+        # fresh tensors (the slot is claimed already; ptr == 0): a release leaves both them and the standing claims alone
+        later = F._GradOuts(cpu)
+        dw2, anon = later.take(wp, (2, 3)), later.take(0, (5,))
+        assert dw2.data_ptr() != slots[wp].data_ptr() and dw2.dtype == torch.float32 and tuple(anon.shape) == (5,)
+        later.release()
+        assert F.GRAD_DEST_STATS['claimed'] == before + 2
+        assert F._grad_acc(wp, (2, 3)) is not None and F._grad_acc(bp, (3,)) is not None
+        outs.release()                                                    # (leave the counter as it was found)
+        assert F.GRAD_DEST_STATS['claimed'] == before
+    assert not F._GRAD_DEST
+
+
 def test_autograd_adopts_a_slot_alias_as_grad():
     """The contract grads_into relies on (torch 2.x AccumulateGrad): an unset .grad adopts, without a copy, a dense gradient tensor
     nobody else holds -- also when it is a view into another buffer; a second contribution is summed out of place."""

@@ -1202,6 +1202,64 @@ def test_from_rgb_backward_in_one_pass(dtype, cin, monkeypatch):
         _mostly_close(a, r, rt, at, name + ' vs separate kernels')
 
 
+def test_declined_fused_from_rgb_backward_under_grads_into(monkeypatch):
+    """from_rgb (1x1x1, 1 -> 32, bias, LeakyReLU) feeding a 3x3x3 32 -> 32 conv inside functional.grads_into: the conv's data
+    gradient offers from_rgb's whole backward to its epilogue (_pw_fused_backward), which claims the slots of from_rgb's filter
+    and bias first.  Where the library declines (W no multiple of 32) the claims must be given back, or the path taken instead
+    finds the slots taken and the gradients reach .grad as tensors of their own; where it accepts they stay.  Either way every
+    .grad IS its slot, nothing is copied, and the values are those of the same backward without grads_into, bit for bit."""
+    import contextlib
+    import saragan_amd
+    from saragan_amd import functional as F
+    from saragan_amd.optimization import StepGraph
+    dtype = torch.bfloat16
+    n, c = 2, 32
+    params = [(rnd((1, 1, 1, 1, c), 171, dtype).float().to(dev())).requires_grad_(True),
+              (rnd((c,), 172, torch.float32) * 0.3).float().to(dev()).requires_grad_(True),
+              (rnd((3, 3, 3, c, c), 173, dtype).float().to(dev()) * 0.1).requires_grad_(True)]
+    fused = []
+    real = F._pw_fused_backward
+    monkeypatch.setattr(F, '_pw_fused_backward', lambda *a: (lambda r: (fused.append(r is not None), r)[1])(real(*a)))
+
+    def backward(sp, into):
+        img = cl(rnd((n, 1, *sp), 174, dtype), dtype).requires_grad_(True)
+        info = F.ActInfo(0.2)
+        h = F.conv3d(img, params[0], 1.0, bias=params[1], act=True, slope=0.2, out_info=info)
+        info.consume(True)          # the conv's data gradient applies from_rgb's mask
+        y = F.conv3d(h, params[2], 0.05, in_info=info)
+        gy = cl(rnd(tuple(y.shape), 175, dtype), dtype)
+        for p in params:
+            p.grad = None
+        flat = torch.zeros(sum(p.numel() for p in params), device=dev())
+        slots, o = {}, 0
+        for p in params:
+            slots[id(p)] = flat[o:o + p.numel()].view(p.shape)
+            o += p.numel()
+        before = dict(F.GRAD_DEST_STATS)
+        with F.grads_into({p.data_ptr(): slots[id(p)] for p in params}) if into else contextlib.nullcontext():
+            torch.autograd.backward(y, gy, inputs=params + [img])
+        if into:
+            for p in params:
+                assert p.grad is not None and p.grad.data_ptr() == slots[id(p)].data_ptr(), 'a .grad is not its slot'
+                StepGraph._land(p, slots)
+            assert F.GRAD_DEST_STATS['claimed'] - before['claimed'] == len(params)
+            assert F.GRAD_DEST_STATS['copied'] == before['copied']
+        return [p.grad.clone() for p in params] + [img.grad.clone()]
+
+    saragan_amd.set_deterministic(True)
+    try:
+        for sp, engages in (((4, 8, 16), False), ((4, 8, 32), True)):
+            del fused[:]
+            got = backward(sp, True)
+            assert fused == [engages], f'{sp}: the fused from_rgb backward {"declined" if engages else "ran"}'
+            ref = backward(sp, False)
+            assert fused == [engages] * 2
+            for name, a, r in zip(('dw from_rgb', 'db from_rgb', 'dw conv', 'd image'), got, ref):
+                assert torch.equal(a, r), f'{sp}: {name} differs from the backward without grads_into'
+    finally:
+        saragan_amd.set_deterministic(False)
+
+
 def test_pixel_norm_backward_in_the_data_gradient_epilogue():
     """The data-gradient conv whose result is the gradient for a pixel-norm stage's output applies that stage's backward
     (pixel norm + LeakyReLU mask) in its epilogue (sg_conv_epilogue.pn_bwd_y): against the two separate passes, conv then

@@ -158,7 +158,7 @@ def main():
         wmat = F._rgb_matrix(w_frgb, 0.5, torch.bfloat16, small_is_cin=True)
         dw, db = torch.zeros(1, 1, 1, 1, cout, device=dev), torch.zeros(cout, device=dev)
         dimg = F.raw_conv(x, w, coef, flip, False, mask_bits=words, mask_slope=0.2,
-                          pw_bwd=dict(x=x_img, wmat=wmat, want_dx=True, dw=dw, db=db, coef=0.5))
+                          pw_bwd=F.PwBwd(x=x_img, wmat=wmat, want_dx=True, dw=dw, db=db, coef=0.5))
         g0 = F.raw_conv(x, w, coef, flip, False, mask_bits=words, mask_slope=0.2)[0]
         ref = F._pw_backward(x_img, g0, w_frgb, 0.5, True)
         print(f'n{n} 32->32 {sp} flip{int(flip)} masked + from_rgb backward epilogue:', 'declined' if dimg is None else 'ran', flush=True)
