@@ -408,6 +408,37 @@ int sg_adam_ema_guarded(float* p, const float* g, float* m, float* v, float* ema
 int sg_optim_step_guarded(int kind, float* p, const float* g, float* s1, float* s2, float* ema, int64_t numel,
                           const float* lr, const int32_t* skip, float h, float eps, int nesterov, float gscale,
                           float ema_decay, sg_stream_t st);
+/* Layer-wise adaptive optimisers (SURFGAN_2D/optim.py:60-80: LAMBOptimizer, AdamWeightDecayOptimizer; rules optim.py:246-267,
+ * 354-398), fused with the EMA update, over ALL variables of a train op per launch.  g is scaled by gscale first:
+ *   m = b1*m + (1-b1)*g;  v = b2*v + (1-b2)*g^2
+ *   AdamW  u = m / (sqrt(v) + eps) + lam*w;                        w -= lr*u              (no bias correction)
+ *   LAMB   u = (m/(1-b1^t)) / (sqrt(v/(1-b2^t)) + eps) + lam*w;    w -= lr*r*u,  r = |w|/|u| if |w| > 0 and |u| > 0 else 1
+ *   (norms over the whole variable, of w before the update);  if (ema) ema -= (1-ema_decay)*(ema - w)
+ * Segment table (DEVICE, built once per train op): p, g, m, v, ema are the bases of flat f32 buffers of `total` elements;
+ *   segs   int64[nseg][4]    {start (a multiple of 4), count, decay flag (lam = flag ? decay : 0), first block}
+ *   blocks int32[nblocks][2] {segment, chunk}: block b covers elements [chunk*SG_SEG_CHUNK, (chunk+1)*SG_SEG_CHUNK) of its
+ *          segment; a segment's ceil(count / SG_SEG_CHUNK) blocks are consecutive, starting at its `first block`.
+ * Elements outside the segments (alignment padding) are neither read nor written.
+ * lr_dev (may be NULL): a DEVICE float read instead of lr.  skip (may be NULL; needs lr_dev): the non-finite guard's flag --
+ * set: parameters, moments and step count stay, only the EMA update runs; clear: exactly the unguarded result.
+ * LAMB is three launches: sg_lamb_moments (updates m, v; block b leaves its sums of w^2 and u^2 in partials[2b], [2b+1]:
+ * f32[2*nblocks]), sg_lamb_ratios (sums each segment's partials in double in a fixed order, writes ratios f32[nseg]) and
+ * sg_lamb_update (recomputes u, updates w and ema).  No atomics: equal inputs give equal bits.  t: the DEVICE int64 count of
+ * applied updates; 1 - b^t is computed from it in double.  advance = 1 (unguarded): sg_lamb_moments uses *t + 1 and
+ * sg_lamb_ratios stores it; advance = 0: *t was advanced by sg_guard_step. */
+#define SG_SEG_CHUNK 4096
+int sg_adamw_ema(float* p, const float* g, float* m, float* v, float* ema, int64_t total, const int64_t* segs,
+                 const int32_t* blocks, int32_t nseg, int32_t nblocks, float lr, const float* lr_dev, const int32_t* skip,
+                 float b1, float b2, float eps, float decay, float gscale, float ema_decay, sg_stream_t st);
+int sg_lamb_moments(const float* p, const float* g, float* m, float* v, int64_t total, const int64_t* segs,
+                    const int32_t* blocks, int32_t nseg, int32_t nblocks, float* partials, const int64_t* t, int32_t advance,
+                    const int32_t* skip, double b1, double b2, float eps, float decay, float gscale, sg_stream_t st);
+int sg_lamb_ratios(const int64_t* segs, int32_t nseg, int32_t nblocks, const float* partials, float* ratios, int64_t* t,
+                   int32_t advance, const int32_t* skip, sg_stream_t st);
+int sg_lamb_update(float* p, const float* m, const float* v, float* ema, int64_t total, const int64_t* segs,
+                   const int32_t* blocks, int32_t nseg, int32_t nblocks, const float* ratios, const int64_t* t, float lr,
+                   const float* lr_dev, const int32_t* skip, double b1, double b2, float eps, float decay, float ema_decay,
+                   sg_stream_t st);
 
 /* ---- validation metrics on device tensors (metrics/swd.py:13-123, metrics/skim_metrics.py:8-45) ---------------- */
 /* One axis of a separable FIR filter over x viewed as [outer, n, inner] (f32, or f64 when `f64` != 0; accumulated in

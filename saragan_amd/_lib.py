@@ -9,6 +9,7 @@ LIB_PATH = os.environ.get('SARAGAN_LIB') or os.path.join(_HERE, 'libsaragan_hip.
 
 SG_F32, SG_BF16 = 0, 1
 SG_OPT_SGD, SG_OPT_MOMENTUM, SG_OPT_ADADELTA = 0, 1, 2
+SG_SEG_CHUNK = 4096      # elements per block of the segmented optimiser launches (sg_adamw_ema, sg_lamb_*)
 SG_EUNSUPPORTED = -4
 SG_WGRAD_ACCUMULATE, SG_WGRAD_CLEAN_WORKSPACE = 1, 2      # sg_conv3d_wgrad_bias_ex flags
 
@@ -111,6 +112,12 @@ SIGNATURES = {
     'sg_guard_step': (C.c_int, [_p, _p, _p, C.c_double, _p, _p, _i32, C.c_double, C.c_double, _p]),
     'sg_adam_ema_guarded': (C.c_int, [_p, _p, _p, _p, _p, _i64, _p, _p, _f, _f, _f, _f, _f, _p]),
     'sg_optim_step_guarded': (C.c_int, [C.c_int, _p, _p, _p, _p, _p, _i64, _p, _p, _f, _f, C.c_int, _f, _f, _p]),
+    'sg_adamw_ema': (C.c_int, [_p, _p, _p, _p, _p, _i64, _p, _p, _i32, _i32, _f, _p, _p, _f, _f, _f, _f, _f, _f, _p]),
+    'sg_lamb_moments': (C.c_int, [_p, _p, _p, _p, _i64, _p, _p, _i32, _i32, _p, _p, _i32, _p, C.c_double, C.c_double, _f, _f,
+                                  _f, _p]),
+    'sg_lamb_ratios': (C.c_int, [_p, _i32, _i32, _p, _p, _p, _i32, _p, _p]),
+    'sg_lamb_update': (C.c_int, [_p, _p, _p, _p, _i64, _p, _p, _i32, _i32, _p, _p, _f, _p, _p, C.c_double, C.c_double, _f, _f,
+                                 _f, _p]),
     'sg_filter_axis': (C.c_int, [_p, _p, _p, _i64, _i32, _i64, C.POINTER(C.c_double), _i32, _i32, _i32, C.c_double, _i32, _p]),
     'sg_swd_gather': (C.c_int, [_p, _p, _p, _p, _p, _i32, _i32, _i32, _i32, _i32, _i32, _i32, _i32, _i32, _p]),
     'sg_desc_normalize_workspace': (_sz, [_i32]),

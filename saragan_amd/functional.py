@@ -1846,6 +1846,83 @@ def optim_step_(kind, p, g, s1, s2, ema, lr, h=0.0, eps=0.0, nesterov=False, gsc
           'sg_optim_step')
 
 
+def segment_table_arrays(segments, total, chunk=_lib.SG_SEG_CHUNK):
+    """Host half of SegmentTable: segments [(start, count, decay flag)] of a flat buffer of `total` elements ->
+    (segs [[start, count, flag, first block]], blocks [[segment, chunk]]) as include/saragan_hip.h lays them out."""
+    segs, blocks, end = [], [], 0
+    for s, (start, count, flag) in enumerate(sorted((int(a), int(b), int(bool(c))) for a, b, c in segments)):
+        if start % 4 or count < 1 or start < end or start + count > total:
+            raise ValueError(f'segment [{start}, {start + count}) of a flat buffer of {total}: starts must be multiples of 4 and '
+                             f'segments disjoint and inside the buffer')
+        end = start + count
+        segs.append([start, count, flag, len(blocks)])
+        blocks.extend([s, c] for c in range((count + chunk - 1) // chunk))
+    if not segs:
+        raise ValueError('a segment table needs at least one segment')
+    return segs, blocks
+
+
+class SegmentTable:
+    """Device table of a train op's variables for the segmented optimiser launches (sg_adamw_ema, sg_lamb_*), with LAMB's
+    workspace: per-block partial sums and per-segment trust ratios.  Built once per train op (it copies to the device);
+    a step only launches with it."""
+
+    def __init__(self, segments, total, device):
+        segs, blocks = segment_table_arrays(segments, total)
+        self.total, self.nseg, self.nblocks = int(total), len(segs), len(blocks)
+        self.segs = torch.tensor(segs, dtype=torch.int64).to(device)
+        self.blocks = torch.tensor(blocks, dtype=torch.int32).to(device)
+        self.partials = torch.zeros(2 * self.nblocks, dtype=torch.float32, device=device)
+        self.ratios = torch.ones(self.nseg, dtype=torch.float32, device=device)
+
+    def check(self, *bufs):
+        _req_cuda(*bufs)
+        for b in bufs:
+            if b is not None and (b.dtype != torch.float32 or not b.is_contiguous() or b.numel() != self.total):
+                raise ValueError(f'the segment table describes contiguous float32 buffers of {self.total} elements')
+
+
+def adamw_ema_(table, p, g, m, v, ema, lr, beta1, beta2, eps=1e-6, decay=0.0, gscale=1.0, ema_decay=0.99, lr_dev=None,
+               skip=None):
+    """In-place AdamW (no bias correction; decay on the table's flagged segments) + EMA over the segments of whole flat f32
+    buffers: ONE launch (sg_adamw_ema).  lr_dev / skip as in adam_ema_."""
+    lib = _lib.load()
+    table.check(p, g, m, v, ema)
+    if skip is not None and lr_dev is None:
+        raise ValueError('adamw_ema_: a guarded launch needs the step size on the device (lr_dev)')
+    mark_packs_stale()      # the kernel rewrites parameters behind torch's version counters
+    check(lib.sg_adamw_ema(_ptr(p), _ptr(g), _ptr(m), _ptr(v), _ptr(ema), table.total, _ptr(table.segs), _ptr(table.blocks),
+                           table.nseg, table.nblocks, float(lr), None if lr_dev is None else _dev_ptr(lr_dev), _ptr(skip),
+                           float(beta1), float(beta2), float(eps), float(decay), float(gscale), float(ema_decay), _stream()),
+          'sg_adamw_ema')
+
+
+def lamb_ema_(table, p, g, m, v, ema, t, lr, beta1, beta2, eps=1e-6, decay=0.0, gscale=1.0, ema_decay=0.99, lr_dev=None,
+              skip=None):
+    """In-place LAMB + EMA over the segments of whole flat f32 buffers: moments and per-block norms (sg_lamb_moments), one
+    trust ratio per segment (sg_lamb_ratios), update (sg_lamb_update) -- three launches whatever the number of segments.
+    t: the int64 [1] device count of applied updates.  Unguarded, the launches advance it; with skip (the guard's flag;
+    needs lr_dev) sg_guard_step has advanced it already, and a set flag leaves everything but the EMA as it was."""
+    lib = _lib.load()
+    table.check(p, g, m, v, ema)
+    _req_cuda(t)
+    if t.dtype != torch.int64:
+        raise TypeError('lamb_ema_: the step count is an int64 device tensor')
+    if skip is not None and lr_dev is None:
+        raise ValueError('lamb_ema_: a guarded launch needs the step size on the device (lr_dev)')
+    mark_packs_stale()      # the kernels rewrite parameters behind torch's version counters
+    advance = 0 if skip is not None else 1
+    tab = (_ptr(table.segs), _ptr(table.blocks), table.nseg, table.nblocks)
+    check(lib.sg_lamb_moments(_ptr(p), _ptr(g), _ptr(m), _ptr(v), table.total, *tab, _ptr(table.partials), _ptr(t), advance,
+                              _ptr(skip), float(beta1), float(beta2), float(eps), float(decay), float(gscale), _stream()),
+          'sg_lamb_moments')
+    check(lib.sg_lamb_ratios(_ptr(table.segs), table.nseg, table.nblocks, _ptr(table.partials), _ptr(table.ratios), _ptr(t),
+                             advance, _ptr(skip), _stream()), 'sg_lamb_ratios')
+    check(lib.sg_lamb_update(_ptr(p), _ptr(m), _ptr(v), _ptr(ema), table.total, *tab, _ptr(table.ratios), _ptr(t), float(lr),
+                             None if lr_dev is None else _dev_ptr(lr_dev), _ptr(skip), float(beta1), float(beta2), float(eps),
+                             float(decay), float(ema_decay), _stream()), 'sg_lamb_update')
+
+
 def segment_sumsq(flat, offsets_dev, nseg, flag=None, accumulate=False):
     """Per-segment sums of squares; flag (a one-element int32 device tensor): also the all-finite test of nonfinite_flag_
     on the values read (sg_segment_sumsq_flag)."""

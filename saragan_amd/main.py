@@ -74,9 +74,9 @@ def build_parser():
                         'of one network, without writing that phase\'s final checkpoint')
     p.add_argument('--ema_beta', type=float, default=0.99)
     p.add_argument('--noise_stddev', type=float, required=True)
-    p.add_argument('--optimizer', type=none_or_str, choices=[None, 'Adam', 'SGD', 'Momentum', 'Adadelta'], default='Adam')
+    p.add_argument('--optimizer', type=none_or_str, choices=[None, 'Adam', 'SGD', 'Momentum', 'Adadelta', 'LAMB', 'AdamW'], default='Adam')
     p.add_argument('--d_use_different_optimizer', default=False, action='store_true')
-    p.add_argument('--d_optimizer', type=none_or_str, choices=[None, 'Adam', 'SGD', 'Momentum', 'Adadelta'], default='Adam')
+    p.add_argument('--d_optimizer', type=none_or_str, choices=[None, 'Adam', 'SGD', 'Momentum', 'Adadelta', 'LAMB', 'AdamW'], default='Adam')
     p.add_argument('--adam_beta1', type=none_or_float, default=0)
     p.add_argument('--d_use_different_beta1', default=False, action='store_true')
     p.add_argument('--d_adam_beta1', type=none_or_float, default=0)
@@ -89,6 +89,10 @@ def build_parser():
     p.add_argument('--momentum', type=none_or_float, default=0.9)
     p.add_argument('--d_use_different_momentum', default=False, action='store_true')
     p.add_argument('--d_momentum', type=none_or_float, default=0.9)
+    p.add_argument('--weight_decay', type=none_or_float, default=0.0,
+                   help='weight-decay rate of --optimizer LAMB / AdamW (SURFGAN_2D/optim.py:60-80); biases are not decayed')
+    p.add_argument('--d_use_different_weight_decay', default=False, action='store_true')
+    p.add_argument('--d_weight_decay', type=none_or_float, default=0.0)
     p.add_argument('--data_mean', default=None, type=float)
     p.add_argument('--data_stddev', default=None, type=float)
     # validation split and in-loop metrics (main.py:255-256,319-333); --compute_FID is accepted and refused (needs a download)
@@ -126,6 +130,8 @@ def finalize_args(args):
         args.d_rho = args.rho
     if not args.d_use_different_momentum:
         args.d_momentum = args.momentum
+    if not args.d_use_different_weight_decay:
+        args.d_weight_decay = args.weight_decay
     for n in ('g', 'd'):       # main.py:384-399: ramp lengths default to half the mixing / stabilising images
         if getattr(args, f'{n}_lr_increase') and not getattr(args, f'{n}_lr_rise_niter'):
             setattr(args, f'{n}_lr_rise_niter', int(args.mixing_nimg / 2))

@@ -156,10 +156,88 @@ class AdadeltaOptimizer(_FusedRule):
         return dict(h=self.rho, eps=self.epsilon, nesterov=False)
 
 
+def decays(name):
+    """exclude_from_weight_decay of SURFGAN_2D/optim.py:70,79 as it applies to this project's variable names: biases are not
+    decayed (its LayerNorm patterns match nothing here)."""
+    return 'bias' not in name
+
+
+class _SegmentedRule(_Optimizer):
+    """Optimisers whose rule differs per variable (weight decay by name, LAMB's per-variable trust ratio): every launch
+    covers all variables of the train op through a device table of their segments of the flat buffers
+    (functional.SegmentTable), derived from flat['offsets'] restricted to `ranges` and cached per (prefix, ranges)."""
+
+    def __init__(self, learning_rate, beta1=0.9, beta2=0.999, weight_decay_rate=0.0, epsilon=1e-6):
+        super().__init__(learning_rate)
+        self.beta1, self.beta2 = float(beta1), float(beta2)
+        self.weight_decay_rate, self.epsilon = float(weight_decay_rate), float(epsilon)
+        self.tables = {}
+
+    def _slots(self, prefix, flat, names):
+        st = self.state.get(prefix)
+        if st is None or st['total'] != flat['total']:
+            self.tables = {k: t for k, t in self.tables.items() if k[0] != prefix}      # (a new flat buffer: new tables)
+        return super()._slots(prefix, flat, names)
+
+    def _table(self, prefix, flat, ranges):
+        """Allocated with the slots: the first apply of a (prefix, ranges) is never a captured one (StepGraph warms up
+        eagerly), later ones only launch."""
+        key = (prefix, tuple(ranges))
+        tab = self.tables.get(key)
+        if tab is None:
+            segs = [(o, n, decays(name)) for name, (o, n) in flat['offsets'].items()
+                    if any(lo <= o and o + n <= lo + ln for lo, ln in ranges)]
+            tab = self.tables[key] = F.SegmentTable(segs, flat['total'], flat['param'].device)
+        return tab
+
+    def _launch(self, tab, flat, st, ema_flat, lr, gscale, ema_decay, lr_dev, skip):
+        raise NotImplementedError
+
+    def apply(self, prefix, flat, ranges, gscale, ema_flat, ema_decay, lr_dev=None, guard=None):
+        st = self._slots(prefix, flat, ('m', 'v'))
+        tab = self._table(prefix, flat, ranges)
+        if guard is not None:      # t counts applied updates only: sg_guard_step advances the device count
+            lr_dev = self._guard_step(guard)
+        elif lr_dev is None:
+            self.t += 1
+        self._launch(tab, flat, st, ema_flat, self.lr_value(), gscale, ema_decay, lr_dev,
+                     None if guard is None else guard['flag'])
+
+
+class AdamWOptimizer(_SegmentedRule):
+    """AdamWeightDecayOptimizer(learning_rate, weight_decay_rate, beta_1, beta_2, epsilon=1e-6) of SURFGAN_2D/optim.py:73-80
+    (rule optim.py:246-267: Adam without bias correction, decay added to the update): one sg_adamw_ema launch per train op."""
+
+    def _launch(self, tab, flat, st, ema_flat, lr, gscale, ema_decay, lr_dev, skip):
+        F.adamw_ema_(tab, flat['param'], flat['grad'], st['m'], st['v'], ema_flat, lr, self.beta1, self.beta2, self.epsilon,
+                     self.weight_decay_rate, gscale, ema_decay, lr_dev=lr_dev, skip=skip)
+
+
+class LAMBOptimizer(_SegmentedRule):
+    """LAMBOptimizer(learning_rate, weight_decay_rate, beta_1, beta_2, epsilon=1e-6) of SURFGAN_2D/optim.py:60-71 (rule
+    optim.py:354-398): bias-corrected Adam direction plus decay, scaled per variable by the trust ratio |w| / |u|.  Three
+    launches per train op (functional.lamb_ema_).  The bias corrections need t itself: it lives on the device
+    (device_step_count), advanced there once per applied train op -- the captured step replays that -- with the host
+    count alongside."""
+
+    def _slots(self, prefix, flat, names):
+        self.device_step_count(flat['param'].device)      # (made from the host count, before this apply advances it)
+        return super()._slots(prefix, flat, names)
+
+    def _launch(self, tab, flat, st, ema_flat, lr, gscale, ema_decay, lr_dev, skip):
+        F.lamb_ema_(tab, flat['param'], flat['grad'], st['m'], st['v'], ema_flat, self.t_dev, lr, self.beta1, self.beta2,
+                    self.epsilon, self.weight_decay_rate, gscale, ema_decay, lr_dev=lr_dev, skip=skip)
+
+
 def get_optimizer(d_lr, g_lr, args):
-    """optimization.py:6-45: Adam / SGD / Adadelta / Momentum (Nesterov), one per network."""
-    def make(kind, lr, b1, b2, rho, momentum):
-        if kind == 'Adam':
+    """optimization.py:6-45: Adam / SGD / Adadelta / Momentum (Nesterov), one per network; LAMB / AdamW as SURFGAN_2D/optim.py:60-80
+    creates them."""
+    def make(kind, lr, b1, b2, rho, momentum, decay):
+        if kind == 'LAMB':
+            return LAMBOptimizer(learning_rate=lr, beta1=b1, beta2=b2, weight_decay_rate=decay, epsilon=1e-6)
+        elif kind == 'AdamW':
+            return AdamWOptimizer(learning_rate=lr, beta1=b1, beta2=b2, weight_decay_rate=decay, epsilon=1e-6)
+        elif kind == 'Adam':
             return AdamOptimizer(learning_rate=lr, beta1=b1, beta2=b2)
         elif kind == 'SGD':
             return GradientDescentOptimizer(learning_rate=lr)
@@ -170,9 +248,10 @@ def get_optimizer(d_lr, g_lr, args):
         print(f"ERROR: optimizer argument {kind} not recognized or implemented")
         raise NotImplementedError
     rho, mom = getattr(args, 'rho', 0.95), getattr(args, 'momentum', 0.9)
-    optimizer_gen = make(args.optimizer, g_lr, args.adam_beta1, args.adam_beta2, rho, mom)
+    wd = getattr(args, 'weight_decay', 0.0)
+    optimizer_gen = make(args.optimizer, g_lr, args.adam_beta1, args.adam_beta2, rho, mom, wd)
     optimizer_disc = make(args.d_optimizer, d_lr, args.d_adam_beta1, args.d_adam_beta2, getattr(args, 'd_rho', rho),
-                          getattr(args, 'd_momentum', mom))
+                          getattr(args, 'd_momentum', mom), getattr(args, 'd_weight_decay', wd))
     return optimizer_gen, optimizer_disc
 
 
