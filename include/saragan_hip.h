@@ -245,7 +245,9 @@ size_t sg_conv3d_wgrad_clean_bytes(const sg_conv_shape* s, sg_dtype dt);
 
 /* Whole backward of a pointwise convolution FROM cin <= 4 channels (from_rgb, pgan/discriminator.py:9-12) in one pass over
  * dy: dw, dbias as sg_conv3d_wgrad_bias, and dx[n,d,h,w,cin] = sum_c dy[..,c] * w_mat[j][c] (w_mat: [cin][cout] f32, the
- * values the forward multiplied with).  Other shapes: SG_EUNSUPPORTED (run sg_conv3d_fwd + sg_conv3d_wgrad_bias). */
+ * values the forward multiplied with).  cout at most 64 sixteen-byte pieces (512 channels in bf16, 256 in f32: a voxel's
+ * lanes add their parts of dx within one wave).  Other shapes: SG_EUNSUPPORTED, nothing touched (run sg_conv3d_fwd +
+ * sg_conv3d_wgrad_bias). */
 int sg_conv3d_pw_bwd(const void* x, const void* dy, const float* w_mat, float* dw_dhwio, float* dbias, void* dx,
                      float coef, void* workspace, size_t workspace_bytes, const sg_conv_shape* s, sg_dtype dt,
                      sg_stream_t st);

@@ -409,7 +409,8 @@ int sg_small_fwd(const void* x, const void* tail, void* y, const sg_conv_shape* 
   int64_t nb = (a.items + 3) / 4;
   if (nb > 256 * 8) nb = 256 * 8;
   const unsigned blocks = (unsigned)nb;
-  SG_KNAME("conv_small_fwd<%s>", dt == SG_BF16 ? "bf16" : "f32");
+  if (dt == SG_BF16) SG_KNAME("conv_small_fwd<bf16>");      // (the macro formats a name once per site: one site per name)
+  else SG_KNAME("conv_small_fwd<f32>");
   if (dt == SG_BF16) {
     switch (s->cin) {
       case 4: small_fwd_cout<bf16_t, 4>(a, s->cout, blocks, st); break;
@@ -478,7 +479,8 @@ int sg_small_wgrad(const void* x, const void* dy, float* dw, float* dbias, float
   a.R = small_rows_per_strip(s, (int)cap * 4);
   a.strips = sg_cdiv(s->h, a.R);
   a.items = (int64_t)s->n * a.strips * a.segs;
-  SG_KNAME("conv_small_wgrad<%s>", dt == SG_BF16 ? "bf16" : "f32");
+  if (dt == SG_BF16) SG_KNAME("conv_small_wgrad<bf16>");      // (the macro formats a name once per site: one site per name)
+  else SG_KNAME("conv_small_wgrad<f32>");
   int rc = dt == SG_BF16 ? small_wgrad_launch<bf16_t>(a, s, nb, st) : small_wgrad_launch<float>(a, s, nb, st);
   if (rc != SG_OK) return rc;
   SG_LAUNCH_CHECK();

@@ -379,9 +379,20 @@ extern "C" size_t sg_conv3d_wgrad_workspace(const sg_conv_shape* s, sg_dtype dt)
 template <typename T, int BM>
 static int launch_wgrad(WgradArgs& a, const sg_conv_shape* s, hipStream_t st) {
   constexpr int ES = (int)sizeof(T);
-  a.g = sg_make_geom(s, BM);
-  sg_conv_shape sy = *s;
-  sy.kd = sy.kh = sy.kw = 1; sy.upsample_in = 0;
+  a.rs = 32 * ES + 16;
+  constexpr size_t LDS_MAX = 160 * 1024;
+  auto lds_of = [&](const sg_tile_geom& t) {      // x halo image + BM dy rows + the row table
+    return (((size_t)t.TN * t.HD * t.HH * t.HW * a.rs + 15) & ~(size_t)15) + (size_t)BM * a.rs + BM * 4;
+  };
+  // The tile with the fewest staged voxels may not fit the LDS once the halo is wide (5x5x5 in f32 on a two-sample tile, 7x7x7
+  // on any full-sized tile): then the best tile of half the voxels, and so on -- the kernel pads the K range of a smaller tile
+  // to BM rows of zeros.  A single voxel's 7x7x7 halo is 343 rows, which always fits.  A correctness path, not a fast one: the
+  // small tiles are restaged by every launch of 28 taps.
+  int bm = BM;
+  for (;; bm >>= 1) {
+    a.g = sg_make_geom(s, bm);
+    if (lds_of(a.g) <= LDS_MAX || bm == 1) break;
+  }
   a.gy = a.g;
   a.gy.PD = a.gy.PH = a.gy.PW = 0;
   a.gy.HD = a.g.TD; a.gy.HH = a.g.TH; a.gy.HW = a.g.TW;
@@ -389,17 +400,17 @@ static int launch_wgrad(WgradArgs& a, const sg_conv_shape* s, hipStream_t st) {
   a.gy.ups = 0;
   const sg_tile_geom& g = a.g;
   const int64_t ntiles = (int64_t)g.nTn * g.nTd * g.nTh * g.nTw;
-  if (ntiles >= (1 << 24)) return SG_EINVAL;
+  // (smaller tiles are more tiles: on the shrunk path the tile index stays within the 2^16 of sg_tile_of's fastdiv contract)
+  if (ntiles >= (1 << 24) || (bm < BM && ntiles >= (1 << 16))) return SG_EINVAL;
   a.ntiles = (int)ntiles;
-  a.rs = 32 * ES + 16;
   const int hv = g.TN * g.HD * g.HH * g.HW;
   a.xbytes = (hv * a.rs + 15) & ~15;
   a.ybytes = BM * a.rs;
   a.fnp = sg_make_fastdiv(32 * ES / 16);
   a.vec_x = ((s->cin * ES) % 16 == 0) ? 1 : 0;
   a.vec_y = ((s->cout * ES) % 16 == 0) ? 1 : 0;
-  const size_t lds = (size_t)a.xbytes + a.ybytes + BM * 4;
-  if (lds > 160 * 1024) return SG_EINVAL;
+  const size_t lds = lds_of(g);
+  if (lds > LDS_MAX) return SG_EINVAL;
   auto kern = conv_wgrad_kernel<T, BM>;
   SG_ALLOW_160K_LDS(kern);
   const int pairs = a.ciT * a.coT;
@@ -1794,7 +1805,9 @@ static int wgrad_bias_impl(const void* x, const void* dy, float* dw, float* dbia
       float* part = reinterpret_cast<float*>(workspace);
       const int ones = (dbias != nullptr && small_is_cin) ? 1 : 0;   // the big side is dy: its column sums are the bias gradient
       SG_KNAME("pw_wgrad_partial");
-      if (pw_dx && !small_is_cin) { prof.done(SG_EUNSUPPORTED); return SG_EUNSUPPORTED; }
+      // (dx: the P = cb / E lanes of a voxel add their parts with wave shuffles, so they have to lie in one wave: a shuffle
+      // across the wave boundary returns the lane's own value, and 128 / 256 lanes would give twice / four times one wave's part)
+      if (pw_dx && (!small_is_cin || cb / E > 64)) { prof.done(SG_EUNSUPPORTED); return SG_EUNSUPPORTED; }
       if (dt == SG_BF16 && cs == 1)
         hipLaunchKernelGGL((pw_wgrad_partial_kernel<bf16_t, 1>), dim3((unsigned)nb), dim3(256), 0, hs, (const bf16_t*)sm,
                            (const bf16_t*)bg, part, nvox, cs, cb, ones, (bf16_t*)pw_dx, pw_wmat);
