@@ -442,6 +442,44 @@ int sg_lamb_update(float* p, const float* m, const float* v, float* ema, int64_t
                    const float* lr_dev, const int32_t* skip, double b1, double b2, float eps, float decay, float ema_decay,
                    sg_stream_t st);
 
+/* ---- discriminator augmentation with adaptive probability (Karras et al. 2020; not in the reference) ------------------
+ * Pixel-blitting transforms only -- axis flips, 90-degree rotations in the (h, w) plane, integer translations with a constant
+ * fill: index gathers, so values are copied bit for bit and the adjoint is another gather.  Per-sample parameters live in
+ * DEVICE memory as int32 params[n][8] = {flip_d, flip_h, flip_w, rot_k, t_d, t_h, t_w, 0}.  `ops` is a mask of SG_AUG_* bits.
+ *
+ * sg_augment_draw: one thread per sample i.  ctr = offset + i, key = seed ^ 0x4155474D454E5431 (the instance noise's key is
+ * `seed` itself: its streams are untouched).  Three Philox4x32-10 blocks, counter {lo32 ctr, hi32 ctr, j, 0}, j = 0, 1, 2:
+ *     block 0: gate flip_w, gate flip_h, gate flip_d, gate rot90
+ *     block 1: gate translate, value flip_w, value flip_h, value flip_d
+ *     block 2: value rot_k, value t_d, value t_h, value t_w
+ *   gate r       : (uint64)r < (uint64)((double)p * 4294967296.0)     (p <= 0 or NaN: never; p >= 1: always)
+ *   value r, cnt : (int)(((uint64)r * cnt) >> 32), uniform in [0, cnt)
+ *   flip_a = gate ? value(2) : 0;  rot_k = gate ? value(4) : 0;  t_a = gate ? value(2 m_a + 1) - m_a : 0  (one gate for all t)
+ * Integer arithmetic only after the conversion of p; a transform whose bit is clear in `ops` yields 0.  p_dev (may be NULL):
+ * a DEVICE float read instead of p.  offset_dev (may be NULL): a DEVICE counter read instead of `offset` and then advanced
+ * by `bump` in stream order (the contract of sg_add_noise_dev: the form a captured step uses).
+ *
+ * sg_augment_apply on NDHWC x, y [n, d, h, w, c] (x != y), params as above:
+ *   forward  y[i] = shift(rot90(flip(x[i], axes), k, plane (h, w)), t, fill)   -- numpy's flip / rot90 conventions on the
+ *            sample's [d, h, w, c] array; shift(a, t, fill)[v] = a[v - t] where v - t is in range, else fill
+ *   adjoint  y[i] = flip(rot90(shift(x[i], -t, 0), -k), axes)                  -- the transpose of the forward's linear part
+ * Only the transforms whose bit is set in `ops` are read from params (rot_k mod 4; every source voxel is range-checked);
+ * SG_AUG_ROT90 with h != w is SG_EINVAL.
+ *
+ * sg_ada_update: the controller of the adaptive probability, one thread.  logits: D's outputs on the real batch (f32 [n]);
+ * state: DEVICE int64[4] = {sum_sign, count, steps, adjustments}; p: DEVICE float.
+ *     sum_sign += sum_i sign(logits[i])  (+1 / -1; 0 for zeros and NaN);  count += n;  steps += 1
+ *     if steps % interval == 0:  up = sum_sign * target_den > target_num * count          (int64)
+ *                                p = min(max(p + (up ? delta : -delta), 0), p_max)        (f32)
+ *                                adjustments += 1;  sum_sign = count = 0 */
+enum { SG_AUG_FLIP_W = 1, SG_AUG_FLIP_H = 2, SG_AUG_FLIP_D = 4, SG_AUG_ROT90 = 8, SG_AUG_TRANSLATE = 16, SG_AUG_ALL = 31 };
+int sg_augment_draw(int32_t* params, int32_t n, uint32_t ops, int32_t m_d, int32_t m_h, int32_t m_w, float p,
+                    const float* p_dev, uint64_t seed, uint64_t offset, uint64_t* offset_dev, uint64_t bump, sg_stream_t st);
+int sg_augment_apply(const void* x, void* y, const int32_t* params, int32_t n, int32_t d, int32_t h, int32_t w, int32_t c,
+                     uint32_t ops, float fill, int32_t adjoint, sg_dtype dt, sg_stream_t st);
+int sg_ada_update(const float* logits, int32_t n, int64_t* state, float* p, int32_t interval, int64_t target_num,
+                  int64_t target_den, float delta, float p_max, sg_stream_t st);
+
 /* ---- validation metrics on device tensors (metrics/swd.py:13-123, metrics/skim_metrics.py:8-45) ---------------- */
 /* One axis of a separable FIR filter over x viewed as [outer, n, inner] (f32, or f64 when `f64` != 0; accumulated in
  * f64 either way): y = alpha * value + add (add may be NULL; it is shaped like y).

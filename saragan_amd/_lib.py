@@ -12,6 +12,8 @@ SG_OPT_SGD, SG_OPT_MOMENTUM, SG_OPT_ADADELTA = 0, 1, 2
 SG_SEG_CHUNK = 4096      # elements per block of the segmented optimiser launches (sg_adamw_ema, sg_lamb_*)
 SG_EUNSUPPORTED = -4
 SG_WGRAD_ACCUMULATE, SG_WGRAD_CLEAN_WORKSPACE = 1, 2      # sg_conv3d_wgrad_bias_ex flags
+# sg_augment_* transform bits
+SG_AUG_FLIP_W, SG_AUG_FLIP_H, SG_AUG_FLIP_D, SG_AUG_ROT90, SG_AUG_TRANSLATE, SG_AUG_ALL = 1, 2, 4, 8, 16, 31
 
 
 class ConvShape(C.Structure):
@@ -118,6 +120,9 @@ SIGNATURES = {
     'sg_lamb_ratios': (C.c_int, [_p, _i32, _i32, _p, _p, _p, _i32, _p, _p]),
     'sg_lamb_update': (C.c_int, [_p, _p, _p, _p, _i64, _p, _p, _i32, _i32, _p, _p, _f, _p, _p, C.c_double, C.c_double, _f, _f,
                                  _f, _p]),
+    'sg_augment_draw': (C.c_int, [_p, _i32, C.c_uint32, _i32, _i32, _i32, _f, _p, _u64, _u64, _p, _u64, _p]),
+    'sg_augment_apply': (C.c_int, [_p, _p, _p, _i32, _i32, _i32, _i32, _i32, C.c_uint32, _f, _i32, C.c_int, _p]),
+    'sg_ada_update': (C.c_int, [_p, _i32, _p, _p, _i32, _i64, _i64, _f, _f, _p]),
     'sg_filter_axis': (C.c_int, [_p, _p, _p, _i64, _i32, _i64, C.POINTER(C.c_double), _i32, _i32, _i32, C.c_double, _i32, _p]),
     'sg_swd_gather': (C.c_int, [_p, _p, _p, _p, _p, _i32, _i32, _i32, _i32, _i32, _i32, _i32, _i32, _i32, _p]),
     'sg_desc_normalize_workspace': (_sz, [_i32]),

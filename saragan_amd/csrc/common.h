@@ -88,6 +88,21 @@ int sg_small_wgrad(const void* x, const void* dy, float* dw, float* dbias, float
 static inline size_t sg_esize(sg_dtype dt) { return dt == SG_BF16 ? 2 : 4; }
 static inline bool sg_aligned16(const void* p) { return (((uintptr_t)p) & 15) == 0; }
 
+// ---- Philox4x32-10 (Salmon et al. 2011): counter (c0..c3), key (k0, k1) -> four 32-bit words.  Shared by the instance noise
+// (elementwise.hip: counter = element index / 4, key = seed) and the augmentation draw (augment.hip).
+__device__ __forceinline__ void philox4x32_10(uint32_t c0, uint32_t c1, uint32_t c2, uint32_t c3, uint32_t k0,
+                                              uint32_t k1, uint32_t out[4]) {
+#pragma unroll
+  for (int rnd = 0; rnd < 10; ++rnd) {
+    const uint32_t hi0 = __umulhi(0xD2511F53u, c0), lo0 = 0xD2511F53u * c0;
+    const uint32_t hi1 = __umulhi(0xCD9E8D57u, c2), lo1 = 0xCD9E8D57u * c2;
+    const uint32_t n0 = hi1 ^ c1 ^ k0, n1 = lo1, n2 = hi0 ^ c3 ^ k1, n3 = lo0;
+    c0 = n0; c1 = n1; c2 = n2; c3 = n3;
+    k0 += 0x9E3779B9u; k1 += 0xBB67AE85u;
+  }
+  out[0] = c0; out[1] = c1; out[2] = c2; out[3] = c3;
+}
+
 // ---- exact unsigned division by a small runtime constant (x < 2^16, d < 2^16) -------------------
 struct sg_fastdiv {
   uint32_t d, m;

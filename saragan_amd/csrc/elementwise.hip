@@ -787,20 +787,7 @@ __global__ void lerp_rows_kernel(const T* __restrict__ a, const T* __restrict__ 
   }
 }
 
-// Philox4x32-10 (Salmon et al. 2011), counter = element index / 4, key = seed.
-__device__ __forceinline__ void philox4x32_10(uint32_t c0, uint32_t c1, uint32_t c2, uint32_t c3, uint32_t k0,
-                                              uint32_t k1, uint32_t out[4]) {
-#pragma unroll
-  for (int rnd = 0; rnd < 10; ++rnd) {
-    const uint32_t hi0 = __umulhi(0xD2511F53u, c0), lo0 = 0xD2511F53u * c0;
-    const uint32_t hi1 = __umulhi(0xCD9E8D57u, c2), lo1 = 0xCD9E8D57u * c2;
-    const uint32_t n0 = hi1 ^ c1 ^ k0, n1 = lo1, n2 = hi0 ^ c3 ^ k1, n3 = lo0;
-    c0 = n0; c1 = n1; c2 = n2; c3 = n3;
-    k0 += 0x9E3779B9u; k1 += 0xBB67AE85u;
-  }
-  out[0] = c0; out[1] = c1; out[2] = c2; out[3] = c3;
-}
-
+// Philox4x32-10: common.h (philox4x32_10); counter = element index / 4, key = seed.
 template <typename T>
 __global__ void add_noise_kernel(const T* __restrict__ x, T* __restrict__ out, float stddev, uint64_t seed,
                                  uint64_t offset, int64_t numel, const uint64_t* __restrict__ offset_dev = nullptr) {

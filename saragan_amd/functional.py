@@ -1644,6 +1644,35 @@ class _AddNoise(torch.autograd.Function):
         return g, None, None, None
 
 
+class _Augment(torch.autograd.Function):
+    """sg_augment_apply: per-sample flips / rot90 / integer translation of an NDHWC batch (forward), or its exact adjoint.
+    The derivative of either with respect to x is the other one with fill 0, so the backward is this Function again with the
+    flag flipped: differentiable to any order (the gradient penalty differentiates through D's data gradient)."""
+
+    @staticmethod
+    def forward(ctx, x, params, fill, ops, adjoint):
+        _note_all(x, params)
+        lib = _lib.load()
+        _req_cuda(x, params)
+        if x.dim() != 5:
+            raise ValueError(f'augment takes a [N,C,D,H,W] tensor, got shape {tuple(x.shape)}')
+        x = ndhwc(x)
+        n, c, d, h, w = _dims(x)
+        if params.dtype != torch.int32 or tuple(params.shape) != (n, 8) or not params.is_contiguous():
+            raise ValueError(f'augment parameters are a contiguous int32 [{n}, 8] tensor, got {params.dtype} {tuple(params.shape)}')
+        y = torch.empty_like(x)
+        check(lib.sg_augment_apply(_ptr(x), _ptr(y), _ptr(params), n, d, h, w, c, int(ops), float(fill), 1 if adjoint else 0,
+                                   _dt(x), _stream()), 'sg_augment_apply')
+        ctx.save_for_backward(params)
+        ctx.ops, ctx.adjoint = int(ops), bool(adjoint)
+        return y
+
+    @staticmethod
+    def backward(ctx, g):
+        (params,) = ctx.saved_tensors
+        return _Augment.apply(g, params, 0.0, ctx.ops, not ctx.adjoint), None, None, None, None
+
+
 class _SumsqKeepW(torch.autograd.Function):
     """out[n, w] = sum_{c,d,h} g^2: tf.reduce_sum(tf.square(g), (1,2,3)) on NCDHW (networks/loss.py:140)."""
 
@@ -1739,6 +1768,70 @@ def interpolate_rows(gamma, a, b):
 
 def add_noise(x, stddev, seed, offset=0):
     return _AddNoise.apply(x, stddev, seed, offset)
+
+
+AUG_OPS = {'flip_w': _lib.SG_AUG_FLIP_W, 'flip_h': _lib.SG_AUG_FLIP_H, 'flip_d': _lib.SG_AUG_FLIP_D, 'rot90': _lib.SG_AUG_ROT90,
+           'translate': _lib.SG_AUG_TRANSLATE}
+AUG_ALL = _lib.SG_AUG_ALL
+
+
+def augment_ops_mask(names):
+    """'flip_w,translate' (or a list of names) -> the SG_AUG_* bit mask."""
+    if isinstance(names, str):
+        names = [s for s in names.split(',') if s]
+    mask = 0
+    for name in names:
+        if name not in AUG_OPS:
+            raise ValueError(f'unknown augmentation {name!r}: choose from {", ".join(AUG_OPS)}')
+        mask |= AUG_OPS[name]
+    return mask
+
+
+def augment_draw(n, ops, max_shift, p, seed, offset=0, device=None):
+    """Per-sample augmentation parameters, int32 [n, 8] = {flip_d, flip_h, flip_w, rot_k, t_d, t_h, t_w, 0}, drawn on the device
+    (sg_augment_draw; the rule is in include/saragan_hip.h).  ops: SG_AUG_* mask; max_shift: (m_d, m_h, m_w).  p: a Python
+    float, or a one-element f32 DEVICE tensor the kernel reads.  offset: a Python int, or a one-element int64 DEVICE tensor
+    read by the kernel and then advanced by 1 << 40 on the device (the forms a captured step uses)."""
+    lib = _lib.load()
+    for t in (p, offset):
+        if torch.is_tensor(t):
+            _req_cuda(t)
+            device = device or t.device
+    out = torch.empty((int(n), 8), dtype=torch.int32, device=device or 'cuda')
+    _req_cuda(out)
+    m_d, m_h, m_w = (int(m) for m in max_shift)
+    p_dev = torch.is_tensor(p)
+    if p_dev and (p.dtype != torch.float32 or p.numel() != 1):
+        raise ValueError('a device-side probability is a one-element float32 tensor')
+    off_dev = torch.is_tensor(offset)
+    if off_dev and (offset.dtype != torch.int64 or offset.numel() != 1):
+        raise ValueError('a device-side Philox offset is a one-element int64 tensor')
+    check(lib.sg_augment_draw(_ptr(out), int(n), int(ops), m_d, m_h, m_w, 0.0 if p_dev else float(p), _ptr(p) if p_dev else None,
+                              int(seed) & (2 ** 64 - 1), 0 if off_dev else int(offset) & (2 ** 64 - 1),
+                              _ptr(offset) if off_dev else None, (1 << 40) if off_dev else 0, _stream()), 'sg_augment_draw')
+    return out
+
+
+def augment(x, params, fill=0.0, ops=AUG_ALL, adjoint=False):
+    """y[i] = shift(rot90(flip(x[i], axes), k, plane (h, w)), t, fill) with sample i's `params` row (augment_draw's layout);
+    adjoint=True: the exact transpose of its linear part.  Only the transforms in `ops` are read from params; rot90 needs
+    h == w.  Values are copied: a permutation reproduces x's bits."""
+    return _Augment.apply(x, params, fill, ops, adjoint)
+
+
+def ada_update_(logits, state, p, interval, target, delta, p_max):
+    """The adaptive augmentation probability's controller (sg_ada_update, one thread; rule in include/saragan_hip.h).
+    logits: D's outputs on the real batch; state: int64 [4] {sum_sign, count, steps, adjustments}; p: f32 [1] (device tensors,
+    updated in place).  target: (numerator, denominator) of the sign statistic's set point."""
+    lib = _lib.load()
+    _req_cuda(logits, state, p)
+    lg = logits.detach().reshape(-1)
+    if lg.dtype != torch.float32 or not lg.is_contiguous():
+        lg = lg.float().contiguous()
+    if state.dtype != torch.int64 or state.numel() != 4 or p.dtype != torch.float32 or p.numel() != 1:
+        raise ValueError('ada_update_: state is int64 [4], p is float32 [1]')
+    check(lib.sg_ada_update(_ptr(lg), lg.numel(), _ptr(state), _ptr(p), int(interval), int(target[0]), int(target[1]),
+                            float(delta), float(p_max), _stream()), 'sg_ada_update')
 
 
 def sumsq_keep_w(g):

@@ -5,7 +5,7 @@ import argparse
 import json
 
 from .networks.pgan.variables import preset_specs
-from .utils import get_base_shape, get_num_phases
+from .utils import get_base_shape, get_num_phases, parse_tuple
 
 
 def none_or_str(v):
@@ -72,6 +72,31 @@ def build_parser():
     p.add_argument('--max_consecutive_nonfinite', type=int, default=None,
                    help='(not in the reference) with --skip_nonfinite_steps: stop with an error after N consecutive skipped steps '
                         'of one network, without writing that phase\'s final checkpoint')
+    # (not in the reference) discriminator augmentation with pixel-blitting transforms (Karras et al. 2020), drawn and applied on
+    # the device: DESIGN.md section 4
+    p.add_argument('--augment', default='none', choices=['none', 'fixed', 'ada'],
+                   help='(not in the reference) augment the real and generated batches before every use by the discriminator: '
+                        'fixed = with probability --augment_p per transform, ada = the probability adapts to the sign of D\'s '
+                        'real-sample logits (logistic loss only; under --horovod each rank adapts on its own shard)')
+    p.add_argument('--augment_p', type=float, default=0.0,
+                   help='(not in the reference) the fixed probability, or the initial one of --augment ada')
+    p.add_argument('--augment_ops', type=str, default='flip_w,translate',
+                   help='(not in the reference) comma list from flip_w,flip_h,flip_d,rot90,translate (rot90 turns the H x W plane '
+                        'and needs it square)')
+    p.add_argument('--augment_max_shift', type=float, default=0.125,
+                   help='(not in the reference) largest translation as a fraction of each extent')
+    p.add_argument('--augment_fill', type=float, default=0.0,
+                   help='(not in the reference) value of the voxels a translation uncovers: the data\'s background value AFTER '
+                        'normalisation (--data_mean / --data_stddev)')
+    p.add_argument('--ada_target', type=float, default=None,
+                   help='(not in the reference) --augment ada: set point of mean sign(D(real)) (default 0.6)')
+    p.add_argument('--ada_interval', type=int, default=None,
+                   help='(not in the reference) --augment ada: steps between two adjustments of p (default 4)')
+    p.add_argument('--ada_kimg', type=float, default=None,
+                   help='(not in the reference) --augment ada: thousands of images over which p can move from 0 to 1 (default 500): '
+                        'an adjustment moves p by batch * interval / (ada_kimg * 1000)')
+    p.add_argument('--ada_p_max', type=float, default=None,
+                   help='(not in the reference) --augment ada: upper limit of p (default 0.8)')
     p.add_argument('--ema_beta', type=float, default=0.99)
     p.add_argument('--noise_stddev', type=float, required=True)
     p.add_argument('--optimizer', type=none_or_str, choices=[None, 'Adam', 'SGD', 'Momentum', 'Adadelta', 'LAMB', 'AdamW'], default='Adam')
@@ -112,6 +137,41 @@ def build_parser():
     return p
 
 
+ADA_DEFAULTS = {'ada_target': 0.6, 'ada_interval': 4, 'ada_kimg': 500.0, 'ada_p_max': 0.8}
+AUGMENT_OPS = ('flip_w', 'flip_h', 'flip_d', 'rot90', 'translate')
+
+
+def finalize_augment_args(args):
+    """The --augment* / --ada_* flags: refusals first, then the defaults of the flags not given."""
+    if not hasattr(args, 'augment'):      # a namespace built without the parser: augmentation off
+        return args
+    given = [k for k in ADA_DEFAULTS if getattr(args, k, None) is not None]
+    if given and args.augment != 'ada':
+        raise SystemExit(f'--{given[0]} needs --augment ada')
+    if args.augment == 'ada' and args.loss_fn == 'wgan':
+        raise SystemExit('--augment ada adapts on the sign of D\'s real-sample logits, which is defined for the logistic loss: '
+                         'use --augment fixed with --loss_fn wgan')
+    ops = [o for o in str(args.augment_ops).split(',') if o]
+    for o in ops:
+        if o not in AUGMENT_OPS:
+            raise SystemExit(f'--augment_ops: unknown transform {o!r} (choose from {",".join(AUGMENT_OPS)})')
+    if args.augment != 'none':
+        shape = parse_tuple(args.final_shape)
+        if 'rot90' in ops and shape[-2] != shape[-1]:
+            raise SystemExit(f'--augment_ops rot90 turns the H x W plane and needs it square, got {shape[-2]} x {shape[-1]}')
+        if not 0.0 <= args.augment_p <= 1.0:
+            raise SystemExit('--augment_p is a probability')
+        if not 0.0 <= args.augment_max_shift <= 1.0:
+            raise SystemExit('--augment_max_shift is a fraction of the extent')
+    for k, v in ADA_DEFAULTS.items():
+        if getattr(args, k, None) is None:
+            setattr(args, k, v)
+    if args.ada_interval < 1 or args.ada_kimg <= 0 or not 0.0 <= args.ada_p_max <= 1.0:
+        raise SystemExit('--ada_interval must be >= 1, --ada_kimg > 0 and --ada_p_max a probability')
+    args.augment_ops = ','.join(ops)
+    return args
+
+
 def finalize_args(args):
     """main.py:384-411 post-parse defaults: the discriminator inherits the generator's optimiser settings unless
     the --d_use_different_* switches are given; presets fill missing kernel/filter specs."""
@@ -120,6 +180,7 @@ def finalize_args(args):
             raise SystemExit('--max_consecutive_nonfinite needs --skip_nonfinite_steps')
         if args.max_consecutive_nonfinite < 1:
             raise SystemExit('--max_consecutive_nonfinite must be >= 1')
+    finalize_augment_args(args)
     if not args.d_use_different_optimizer:
         args.d_optimizer = args.optimizer
     if not args.d_use_different_beta1:

@@ -17,6 +17,7 @@ class RandomSource:
     def __init__(self, seed=0, device='cuda'):
         self.seed = int(seed)
         self.calls = 0
+        self.aug_calls = 0      # augmentation draws count on their own: add_noise's offsets are the same with and without them
         self.gen = torch.Generator(device=device).manual_seed(self.seed)
 
     def latent(self, n, latent_dim, device):
@@ -29,6 +30,61 @@ class RandomSource:
         self.calls += 1
         return F.add_noise(x, stddev, self.seed, offset=self.calls << 40)
 
+    def augment(self, x, tag):
+        cfg = _AUGMENT['cfg']
+        self.aug_calls += 1
+        params = F.augment_draw(x.shape[0], cfg.ops, cfg.max_shifts(x), cfg.p, self.seed, offset=self.aug_calls << 40,
+                                device=x.device)
+        return F.augment(x, params, cfg.fill, cfg.ops)
+
+
+class AugmentConfig:
+    """Discriminator augmentation (not in the reference; Karras et al. 2020): real and generated batches pass through the same
+    family of random pixel-blitting transforms -- flips, 90-degree rotations in the (h, w) plane, integer translations -- before
+    every use by D.  mode 'none' (default: no launch is added anywhere), 'fixed' (p a host float) or 'ada' (p a one-element
+    DEVICE float that sg_ada_update moves by `delta` every `interval` calls, towards the sign statistic of D's real-sample logits
+    meeting `target`)."""
+
+    def __init__(self, mode='none', ops=0, max_shift=0.125, fill=0.0, p=0.0, interval=4, target=0.6, delta=0.0, p_max=0.8,
+                 device=None):
+        if mode not in ('none', 'fixed', 'ada'):
+            raise ValueError(f'unknown augmentation mode {mode!r}')
+        self.mode, self.ops, self.max_shift, self.fill = mode, int(ops), float(max_shift), float(fill)
+        self.interval, self.delta, self.p_max = int(interval), float(delta), float(p_max)
+        self.target = (int(round(float(target) * 1000000)), 1000000)
+        self.state = None
+        if mode == 'ada':      # the probability and the controller's sums live on the device: a captured step replays them
+            self.p = torch.tensor([float(p)], dtype=torch.float32, device=device or 'cuda')
+            self.state = torch.zeros(4, dtype=torch.int64, device=device or 'cuda')
+        else:
+            self.p = float(p)
+
+    @property
+    def on(self):
+        return self.mode != 'none'
+
+    def max_shifts(self, x):
+        """Largest shift per axis: the configured fraction of each extent of the [N,C,D,H,W] batch, rounded down."""
+        return tuple(int(self.max_shift * e) for e in x.shape[2:])
+
+    def update(self, disc_real):
+        if self.mode == 'ada':
+            F.ada_update_(disc_real, self.state, self.p, self.interval, self.target, self.delta, self.p_max)
+
+
+_AUGMENT = {'cfg': AugmentConfig()}
+
+
+def set_augment(cfg=None):
+    """Installs an AugmentConfig (None: augmentation off) for the forward functions below; returns the previous one."""
+    prev = _AUGMENT['cfg']
+    _AUGMENT['cfg'] = cfg if cfg is not None else AugmentConfig()
+    return prev
+
+
+def _augment(rng, x, tag):
+    return rng.augment(x, tag) if _AUGMENT['cfg'].on else x
+
 
 _DEVICE_RANDOM = RandomSource      # (the class itself: tests substitute `RandomSource` with host-drawn variants)
 
@@ -37,7 +93,7 @@ def graph_safe(src):
     """Whether a captured step (loss.StaticRandom) can stand in for `src`: the device-side source with none of its draws
     overridden."""
     return (type(src) is _DEVICE_RANDOM or (isinstance(src, _DEVICE_RANDOM) and all(
-        getattr(type(src), m) is getattr(_DEVICE_RANDOM, m) for m in ('latent', 'gamma', 'add_noise')))) and \
+        getattr(type(src), m) is getattr(_DEVICE_RANDOM, m) for m in ('latent', 'gamma', 'add_noise', 'augment')))) and \
         hasattr(src, 'calls') and hasattr(src, 'gen')
 
 
@@ -56,6 +112,14 @@ class InjectedRandom(RandomSource):
     def add_noise(self, x, stddev, tag):
         noise = self.t[tag].to(x.device, x.dtype)
         return F.lerp(x, noise.contiguous(memory_format=torch.channels_last_3d), 1.0, float(stddev))
+
+    def augment(self, x, tag):
+        """keys aug_real / aug_fake: int [N, 8] parameter rows (functional.augment_draw's layout); absent: identity."""
+        cfg = _AUGMENT['cfg']
+        params = self.t.get(tag)
+        if params is None:
+            params = torch.zeros(x.shape[0], 8, dtype=torch.int32)
+        return F.augment(x, params.to(x.device, torch.int32).contiguous(), cfg.fill, cfg.ops)
 
 
 class StaticRandom:
@@ -76,6 +140,8 @@ class StaticRandom:
         self._iz = self._ig = 0
         self.counter = torch.zeros(1, dtype=torch.int64, device=device)
         self.noise_calls = 0         # add_noise calls of one step (counted while capturing)
+        self.aug_counter = torch.zeros(1, dtype=torch.int64, device=device)      # the augmentation draws' Philox offset
+        self.aug_calls = 0           # augment calls of one step (counted while capturing)
         self.counting = False
 
     def draw(self):
@@ -93,6 +159,8 @@ class StaticRandom:
     def sync_counter(self):
         if getattr(self, '_synced_calls', None) != self.base.calls:      # (only after eager steps moved the host count on)
             self.counter.fill_((self.base.calls + 1) << 40)
+        if getattr(self, '_synced_aug_calls', None) != self.base.aug_calls:
+            self.aug_counter.fill_((self.base.aug_calls + 1) << 40)
 
     def latent(self, n, latent_dim, device):
         assert (int(n), int(latent_dim)) == (self.n, self.latent_dim)
@@ -111,9 +179,19 @@ class StaticRandom:
             self.noise_calls += 1
         return F.add_noise(x, stddev, self.base.seed, offset=self.counter)
 
+    def augment(self, x, tag):
+        cfg = _AUGMENT['cfg']
+        if self.counting:
+            self.aug_calls += 1
+        params = F.augment_draw(x.shape[0], cfg.ops, cfg.max_shifts(x), cfg.p, self.base.seed, offset=self.aug_counter,
+                                device=x.device)
+        return F.augment(x, params, cfg.fill, cfg.ops)
+
     def after_replay(self):
         self.base.calls += self.noise_calls
         self._synced_calls = self.base.calls      # the device counter moved on by the same amount
+        self.base.aug_calls += self.aug_calls
+        self._synced_aug_calls = self.base.aug_calls
 
 
 _RANDOM = {'src': None}
@@ -126,7 +204,8 @@ class linear_generator_link:
     With the wgan loss d gen_loss / d D(fake) = -1/N = -(d disc_loss / d D(fake)) element for element, and the
     discriminator's data-gradient chain is linear in its upstream gradient, so the gradient of gen_loss at the
     discriminator's INPUT is exactly minus what the disc_loss backward delivers there.  Inside this context the fake
-    batch enters D through a detached leaf and gen_loss carries `.sg_link = (gen_sample_noisy, leaf, -1.0)`: the
+    batch enters D through a detached leaf and gen_loss carries `.sg_link = (gen_sample_noisy, leaf, -1.0)` (with the
+    discriminator augmentation on, gen_sample_noisy is the AUGMENTED fake: G's backward passes through the augment adjoint): the
     caller back-propagates disc_loss to `leaf` along with D's variables and then starts the generator's backward at
     gen_sample_noisy with factor * leaf.grad — one whole data-gradient pass through D less per step
     (optimization.py:128-163 computes the two tf.gradients separately).  Only exact for a uniform factor (wgan);
@@ -164,6 +243,9 @@ def forward_generator(generator, discriminator, real_image_input, latent_dim, al
                            filter_spec=filter_spec, param=leakiness, is_reuse=is_reuse)
     real_image_input = rng.add_noise(_img(real_image_input), noise_stddev, 'noise_real')  # drawn as in the reference
     gen_sample_noisy = rng.add_noise(gen_sample, noise_stddev, 'noise_fake')
+    # (not in the reference) discriminator augmentation: after the instance noise, before every use by D
+    real_image_input = _augment(rng, real_image_input, 'aug_real')
+    gen_sample_noisy = _augment(rng, gen_sample_noisy, 'aug_fake')
     disc_fake_g = discriminator(gen_sample_noisy, alpha, phase, latent_dim=latent_dim, activation=activation,
                                 kernel_spec=kernel_spec, filter_spec=filter_spec, param=leakiness,
                                 is_reuse=is_reuse).float()
@@ -201,10 +283,14 @@ def forward_discriminator(generator, discriminator, real_image_input, latent_dim
                                filter_spec=filter_spec, param=leakiness, is_reuse=is_reuse)
     real_image_input = rng.add_noise(_img(real_image_input), noise_stddev, 'noise_real')
     gen_sample_noisy = rng.add_noise(gen_sample, noise_stddev, 'noise_fake')
+    # (not in the reference) discriminator augmentation: after the instance noise, before every use by D
+    real_image_input = _augment(rng, real_image_input, 'aug_real')
+    gen_sample_noisy = _augment(rng, gen_sample_noisy, 'aug_fake')
     net = dict(latent_dim=latent_dim, activation=activation, kernel_spec=kernel_spec, filter_spec=filter_spec,
                param=leakiness)
     disc_fake_d = discriminator(gen_sample_noisy.detach(), alpha, phase, **net).float()
     disc_real = discriminator(real_image_input, alpha, phase, is_reuse=True, **net).float()
+    _AUGMENT['cfg'].update(disc_real)
     gamma = rng.gamma(real_image_input.shape[0], real_image_input.device)
     interpolates = F.interpolate_rows(gamma, real_image_input, gen_sample_noisy)      # f32 weights, one rounding
     slopes = torch.sqrt(_gradient_slopes_sq(discriminator, interpolates, alpha, phase, latent_dim, activation,
@@ -235,6 +321,9 @@ def forward_simultaneous(generator, discriminator, real_image_input, latent_dim,
                            filter_spec=filter_spec, param=leakiness, conditioning=conditioning)
     real_image_input = rng.add_noise(_img(real_image_input), noise_stddev, 'noise_real')
     gen_sample_noisy = rng.add_noise(gen_sample, noise_stddev, 'noise_fake')
+    # (not in the reference) discriminator augmentation: after the instance noise, before every use by D
+    real_image_input = _augment(rng, real_image_input, 'aug_real')
+    gen_sample_noisy = _augment(rng, gen_sample_noisy, 'aug_fake')
     net = dict(latent_dim=latent_dim, activation=activation, kernel_spec=kernel_spec, filter_spec=filter_spec,
                param=leakiness, conditioning=conditioning)
     # The reference evaluates D(stop_gradient(fake)) for the D loss and D(fake) for the G loss (loss.py:126-128,
@@ -255,6 +344,7 @@ def forward_simultaneous(generator, discriminator, real_image_input, latent_dim,
         disc_fake_g = discriminator(fake_in, alpha, phase, **net).float()
         disc_fake_d = disc_fake_g
         disc_real = discriminator(real_image_input, alpha, phase, is_reuse=True, **net).float()
+    _AUGMENT['cfg'].update(disc_real)
     gamma = rng.gamma(real_image_input.shape[0], real_image_input.device)
     interpolates = F.interpolate_rows(gamma, real_image_input, gen_sample_noisy)      # f32 weights, one rounding
     # quirk Q1 belongs to the 3-D tree's 5-D tensors; the 2-D tree reduces its 4-D gradient over every non-batch axis

@@ -37,8 +37,30 @@ def get_numpy_dataset(phase, starting_phase, start_shape, dataset_path, scratch_
                             is_correct_phase=phase >= starting_phase, rank=rank, world_size=world, seed=seed)
 
 
+def augment_config(args, device):
+    """The --augment* / --ada_* flags (main.py; not in the reference) -> loss.AugmentConfig, or None with --augment none.  One
+    object for the whole run: the probability and the controller's sums persist across phases."""
+    mode = getattr(args, 'augment', 'none') or 'none'
+    if mode == 'none':
+        return None
+    from . import functional as F
+    return L.AugmentConfig(mode, ops=F.augment_ops_mask(getattr(args, 'augment_ops', 'flip_w,translate')),
+                           max_shift=getattr(args, 'augment_max_shift', 0.125), fill=getattr(args, 'augment_fill', 0.0),
+                           p=getattr(args, 'augment_p', 0.0), interval=getattr(args, 'ada_interval', None) or 4,
+                           target=getattr(args, 'ada_target', None) or 0.6, p_max=getattr(args, 'ada_p_max', None) or 0.8,
+                           device=device)
+
+
 def run_training(args, device=None, max_steps_per_phase=None, log_every=1):
     """optuna_objective(trial=None, args, config).  Returns a dict with per-phase statistics."""
+    prev_augment = L.set_augment(None)      # (_run_training installs the run's own; the caller's comes back afterwards)
+    try:
+        return _run_training(args, device, max_steps_per_phase, log_every)
+    finally:
+        L.set_augment(prev_augment)
+
+
+def _run_training(args, device, max_steps_per_phase, log_every):
     rank, world, local = parallel.init_distributed()
     horovod = bool(getattr(args, 'horovod', False)) and world > 1
     global_size = world if horovod else 1
@@ -64,6 +86,8 @@ def run_training(args, device=None, max_steps_per_phase=None, log_every=1):
     var_list = []
     global_step = 0
     stats = {}
+    aug = augment_config(args, device)
+    L.set_augment(aug)
 
     for phase in range(1, ending_phase + 1):
         np.random.seed(seed); random.seed(seed); torch.manual_seed(seed)   # :102-109
@@ -90,6 +114,8 @@ def run_training(args, device=None, max_steps_per_phase=None, log_every=1):
             if batch_size > max_local_batch_size:
                 batch_size = int(max_local_batch_size)
             assert batch_size * global_size <= args.max_global_batch_size
+        if aug is not None:      # one adjustment moves p by the share of --ada_kimg that `interval` steps show
+            aug.delta = batch_size * global_size * aug.interval / ((getattr(args, 'ada_kimg', None) or 500.0) * 1000.0)
         real_image_input = opt.Placeholder(get_current_input_shape(phase, batch_size, args.start_shape))
         num_metric_samples = get_num_metric_samples(getattr(args, 'num_metric_samples', None), batch_size, global_size)  # :144
         calc_metrics = bool(getattr(args, 'calc_metrics', False)) and npy_data_validation is not None
@@ -212,6 +238,8 @@ def run_training(args, device=None, max_steps_per_phase=None, log_every=1):
             if want_log:
                 print_summary_to_stdout(global_step, int(in_phase_step), img_s, local_img_s, d_loss, g_loss,
                                         float(d_lr_val), float(g_lr_val), alpha)
+            if aug is not None and want_log:      # (the log line above has synchronised already: no sync on other steps)
+                print(f"Augmentation probability: {float(aug.p):.6f}")
             if graph.guard is not None and (local_step // batch_size - 1) % log_every == 0:
                 # at the log point (every rank: the reduced gradients, hence the skips, are the same on all of them)
                 rep = graph.guard_report()
@@ -236,6 +264,8 @@ def run_training(args, device=None, max_steps_per_phase=None, log_every=1):
             graph.check_nonfinite(global_step, graph.guard_report())
         stats[phase] = dict(img_s=imgs / max(1e-9, time.time() - t_phase), d_loss=d_loss, g_loss=g_loss,
                             batch_size=batch_size, steps=local_step // batch_size)
+        if aug is not None:
+            stats[phase]['augment_p'] = float(aug.p)
         # quirk Q5: the end-of-phase checkpoint holds the EMA weights of G AND D; the next phase starts from them
         sess.run(ema.ema_update_weights())
         if horovod:
