@@ -480,6 +480,50 @@ int sg_augment_apply(const void* x, void* y, const int32_t* params, int32_t n, i
 int sg_ada_update(const float* logits, int32_t n, int64_t* state, float* p, int32_t interval, int64_t target_num,
                   int64_t target_den, float delta, float p_max, sg_stream_t st);
 
+/* ---- intensity and fractional-geometry augmentation (Karras et al. 2020: "geom" and "color"; not in the reference) --------
+ * Isotropic scaling, rotation in the (h, w) plane, sub-voxel translation, brightness, contrast: one trilinear resampling pass
+ * with an exact, deterministic adjoint (a gather: no atomics).  `ops` is a mask of SG_AUGF_* bits, a mask of its own next to
+ * SG_AUG_*.  Per-sample parameters live in DEVICE memory as float params[n][16]:
+ *     [0..11] row-major 3 x 4 matrix A: the SOURCE coordinate of output voxel v = (vd, vh, vw) is u = A[:, :3] v + A[:, 3],
+ *             in voxel units;  [12] gain a;  [13] bias b;  [14..15] 0.
+ *
+ * sg_augment_affine_draw: one thread per sample i.  p / p_dev / offset / offset_dev / bump as sg_augment_draw; key =
+ * seed ^ 0x4155474D454E5432; three Philox4x32-10 blocks, counter {lo32 ctr, hi32 ctr, j, 0}, j = 0, 1, 2:
+ *     block 0: gate scale, gate rotate, gate shift, gate brightness
+ *     block 1: gate contrast, value scale, value angle, value brightness
+ *     block 2: value contrast, value t_d, value t_h, value t_w
+ *   gate(r) as sg_augment_draw;  a value word r becomes sym = 2 (r 2^-32) - 1; everything below in double:
+ *   s = exp2(sym log2 max_scale);  theta = sym max_angle (radians);  t_a = sym_a max_shift_a (voxels);
+ *   b = sym max_brightness;  a = exp2(sym log2 max_contrast);  disabled or gated off: s = 1, theta = 0, t = 0, b = 0, a = 1.
+ *   With c_a = (extent_a - 1) / 2:  u = c + (1/s) R(-theta) (v - c - t),  R(-theta) = [[cos, sin], [-sin, cos]] on (h, w):
+ *     A = [[1/s, 0, 0, o_d], [0, cos/s, sin/s, o_h], [0, -sin/s, cos/s, o_w]],  o = c - A[:, :3] (c + t)
+ *   rounded to f32 once.  With every gate off the row is EXACTLY the identity matrix, a = 1, b = 0.
+ *   SG_EINVAL: unknown bits in ops, max_scale outside [1, 2], max_angle outside [0, pi], a negative maximum, max_contrast
+ *   outside [1, 4] (NaN is outside).
+ *
+ * sg_augment_affine_apply on NDHWC x, y [n, d, h, w, c], f32 or bf16, x != y.  flags bit 0: adjoint; bit 1: linear part only
+ * (fill and b read as 0).  Every product and sum below rounds to f32 on its own (no FMA):
+ *   1. u_a = ((A[a][0] vd + A[a][1] vh) + A[a][2] vw) + A[a][3]
+ *   2. support: -1 < u_a < extent_a on every axis, tested in float (NaN fails).  Outside: forward y = a fill (then step 5's
+ *      bias); the adjoint gets nothing from this voxel.
+ *   3. f_a = floor(u_a), r_a = u_a - f_a, w0_a = 1 + (-r_a), w1_a = r_a
+ *   4. corner k = 4 bd + 2 bh + bw: W_k = ((wd wh) ww) a, value x[f + bits]; outside the volume: `fill` forward, absent adjoint
+ *   5. forward: corners in ascending k, W_k == 0 skipped and never read; acc = the first W_k x_k, the later ones added;
+ *      y = b != 0 ? acc + b : acc, rounded to the output type once.  An identity row reproduces every finite input's bits.
+ *   6. adjoint: gx[u] = sum of W_k(v) gy[v] over the output voxels v that have u among their in-range corners with W_k != 0,
+ *      in ascending linear order of v, starting from the first term, rounded once; 0 where no v reaches u.  The kernel
+ *      gathers over a window of candidate v around A^-1 (u - A[:, 3]) whose half-width per axis is the absolute row sum of
+ *      A^-1 plus a slack; absolute row sums above 3 are outside the adjoint's contract.  For ANY bit pattern in params both
+ *      directions stay inside their buffers and the window loops stay within 8 candidates per axis. */
+enum { SG_AUGF_SCALE = 32, SG_AUGF_ROTATE = 64, SG_AUGF_SHIFT = 128, SG_AUGF_BRIGHTNESS = 256, SG_AUGF_CONTRAST = 512,
+       SG_AUGF_ALL = 992 };
+int sg_augment_affine_draw(float* params, int32_t n, uint32_t ops, int32_t d, int32_t h, int32_t w, double max_scale,
+                           double max_angle, double max_shift_d, double max_shift_h, double max_shift_w, double max_brightness,
+                           double max_contrast, float p, const float* p_dev, uint64_t seed, uint64_t offset, uint64_t* offset_dev,
+                           uint64_t bump, sg_stream_t st);
+int sg_augment_affine_apply(const void* x, void* y, const float* params, int32_t n, int32_t d, int32_t h, int32_t w, int32_t c,
+                            float fill, uint32_t flags, sg_dtype dt, sg_stream_t st);
+
 /* ---- validation metrics on device tensors (metrics/swd.py:13-123, metrics/skim_metrics.py:8-45) ---------------- */
 /* One axis of a separable FIR filter over x viewed as [outer, n, inner] (f32, or f64 when `f64` != 0; accumulated in
  * f64 either way): y = alpha * value + add (add may be NULL; it is shaped like y).

@@ -14,6 +14,9 @@ SG_EUNSUPPORTED = -4
 SG_WGRAD_ACCUMULATE, SG_WGRAD_CLEAN_WORKSPACE = 1, 2      # sg_conv3d_wgrad_bias_ex flags
 # sg_augment_* transform bits
 SG_AUG_FLIP_W, SG_AUG_FLIP_H, SG_AUG_FLIP_D, SG_AUG_ROT90, SG_AUG_TRANSLATE, SG_AUG_ALL = 1, 2, 4, 8, 16, 31
+# sg_augment_affine_* transform bits (a mask of their own) and apply flags
+SG_AUGF_SCALE, SG_AUGF_ROTATE, SG_AUGF_SHIFT, SG_AUGF_BRIGHTNESS, SG_AUGF_CONTRAST, SG_AUGF_ALL = 32, 64, 128, 256, 512, 992
+SG_AUGF_ADJOINT, SG_AUGF_LINEAR = 1, 2
 
 
 class ConvShape(C.Structure):
@@ -123,6 +126,9 @@ SIGNATURES = {
     'sg_augment_draw': (C.c_int, [_p, _i32, C.c_uint32, _i32, _i32, _i32, _f, _p, _u64, _u64, _p, _u64, _p]),
     'sg_augment_apply': (C.c_int, [_p, _p, _p, _i32, _i32, _i32, _i32, _i32, C.c_uint32, _f, _i32, C.c_int, _p]),
     'sg_ada_update': (C.c_int, [_p, _i32, _p, _p, _i32, _i64, _i64, _f, _f, _p]),
+    'sg_augment_affine_draw': (C.c_int, [_p, _i32, C.c_uint32, _i32, _i32, _i32, C.c_double, C.c_double, C.c_double, C.c_double,
+                                         C.c_double, C.c_double, C.c_double, _f, _p, _u64, _u64, _p, _u64, _p]),
+    'sg_augment_affine_apply': (C.c_int, [_p, _p, _p, _i32, _i32, _i32, _i32, _i32, _f, C.c_uint32, C.c_int, _p]),
     'sg_filter_axis': (C.c_int, [_p, _p, _p, _i64, _i32, _i64, C.POINTER(C.c_double), _i32, _i32, _i32, C.c_double, _i32, _p]),
     'sg_swd_gather': (C.c_int, [_p, _p, _p, _p, _p, _i32, _i32, _i32, _i32, _i32, _i32, _i32, _i32, _i32, _p]),
     'sg_desc_normalize_workspace': (_sz, [_i32]),

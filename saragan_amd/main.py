@@ -72,8 +72,8 @@ def build_parser():
     p.add_argument('--max_consecutive_nonfinite', type=int, default=None,
                    help='(not in the reference) with --skip_nonfinite_steps: stop with an error after N consecutive skipped steps '
                         'of one network, without writing that phase\'s final checkpoint')
-    # (not in the reference) discriminator augmentation with pixel-blitting transforms (Karras et al. 2020), drawn and applied on
-    # the device: DESIGN.md section 4
+    # (not in the reference) discriminator augmentation (Karras et al. 2020) with pixel-blitting, fractional-geometry and
+    # intensity transforms, drawn and applied on the device: DESIGN.md section 4
     p.add_argument('--augment', default='none', choices=['none', 'fixed', 'ada'],
                    help='(not in the reference) augment the real and generated batches before every use by the discriminator: '
                         'fixed = with probability --augment_p per transform, ada = the probability adapts to the sign of D\'s '
@@ -81,10 +81,20 @@ def build_parser():
     p.add_argument('--augment_p', type=float, default=0.0,
                    help='(not in the reference) the fixed probability, or the initial one of --augment ada')
     p.add_argument('--augment_ops', type=str, default='flip_w,translate',
-                   help='(not in the reference) comma list from flip_w,flip_h,flip_d,rot90,translate (rot90 turns the H x W plane '
-                        'and needs it square)')
+                   help='(not in the reference) comma list from flip_w,flip_h,flip_d,rot90,translate (pixel blitting; rot90 turns '
+                        'the H x W plane and needs it square) and scale,rotate,shift,brightness,contrast (one trilinear resampling '
+                        'pass: isotropic scale, rotation of the H x W plane by any angle, sub-voxel shift, additive brightness, '
+                        'multiplicative contrast)')
     p.add_argument('--augment_max_shift', type=float, default=0.125,
                    help='(not in the reference) largest translation as a fraction of each extent')
+    p.add_argument('--augment_max_scale', type=float, default=1.25,
+                   help='(not in the reference) scale: the factor is log-uniform in [1/max, max], max in [1, 2]')
+    p.add_argument('--augment_max_angle', type=float, default=180.0,
+                   help='(not in the reference) rotate: the angle is uniform in [-max, max] degrees, max in [0, 180]')
+    p.add_argument('--augment_max_brightness', type=float, default=0.2,
+                   help='(not in the reference) brightness: the bias is uniform in [-max, max], in units of the normalised data')
+    p.add_argument('--augment_max_contrast', type=float, default=1.5,
+                   help='(not in the reference) contrast: the gain is log-uniform in [1/max, max], max in [1, 4]')
     p.add_argument('--augment_fill', type=float, default=0.0,
                    help='(not in the reference) value of the voxels a translation uncovers: the data\'s background value AFTER '
                         'normalisation (--data_mean / --data_stddev)')
@@ -138,7 +148,7 @@ def build_parser():
 
 
 ADA_DEFAULTS = {'ada_target': 0.6, 'ada_interval': 4, 'ada_kimg': 500.0, 'ada_p_max': 0.8}
-AUGMENT_OPS = ('flip_w', 'flip_h', 'flip_d', 'rot90', 'translate')
+AUGMENT_OPS = ('flip_w', 'flip_h', 'flip_d', 'rot90', 'translate', 'scale', 'rotate', 'shift', 'brightness', 'contrast')
 
 
 def finalize_augment_args(args):
@@ -163,6 +173,15 @@ def finalize_augment_args(args):
             raise SystemExit('--augment_p is a probability')
         if not 0.0 <= args.augment_max_shift <= 1.0:
             raise SystemExit('--augment_max_shift is a fraction of the extent')
+    # (the affine family's ranges are the ones sg_augment_affine_draw accepts: refused here whatever --augment is)
+    if not 1.0 <= getattr(args, 'augment_max_scale', 1.25) <= 2.0:
+        raise SystemExit('--augment_max_scale is a factor between 1 and 2')
+    if not 0.0 <= getattr(args, 'augment_max_angle', 180.0) <= 180.0:
+        raise SystemExit('--augment_max_angle is an angle between 0 and 180 degrees')
+    if not 0.0 <= getattr(args, 'augment_max_brightness', 0.2) < float('inf'):
+        raise SystemExit('--augment_max_brightness must be >= 0')
+    if not 1.0 <= getattr(args, 'augment_max_contrast', 1.5) <= 4.0:
+        raise SystemExit('--augment_max_contrast is a factor between 1 and 4')
     for k, v in ADA_DEFAULTS.items():
         if getattr(args, k, None) is None:
             setattr(args, k, v)

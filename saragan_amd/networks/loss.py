@@ -2,6 +2,7 @@
 the reference's signatures and return tuples.  Random draws go through a RandomSource so that parity tests can
 inject z, both noise tensors and gamma (TF and torch RNG streams cannot be matched); by default z/gamma come from
 the torch CUDA generator and the instance noise from the library's Philox kernel (sg_add_noise)."""
+import math
 import os
 
 import torch
@@ -31,25 +32,27 @@ class RandomSource:
         return F.add_noise(x, stddev, self.seed, offset=self.calls << 40)
 
     def augment(self, x, tag):
-        cfg = _AUGMENT['cfg']
         self.aug_calls += 1
-        params = F.augment_draw(x.shape[0], cfg.ops, cfg.max_shifts(x), cfg.p, self.seed, offset=self.aug_calls << 40,
-                                device=x.device)
-        return F.augment(x, params, cfg.fill, cfg.ops)
+        return _draw_and_augment(_AUGMENT['cfg'], x, self.seed, self.aug_calls << 40)
 
 
 class AugmentConfig:
     """Discriminator augmentation (not in the reference; Karras et al. 2020): real and generated batches pass through the same
-    family of random pixel-blitting transforms -- flips, 90-degree rotations in the (h, w) plane, integer translations -- before
-    every use by D.  mode 'none' (default: no launch is added anywhere), 'fixed' (p a host float) or 'ada' (p a one-element
+    family of random transforms before every use by D: pixel blitting (flips, 90-degree rotations in the (h, w) plane, integer
+    translations; the SG_AUG_* bits of `ops`), then one trilinear resampling pass (isotropic scale up to `max_scale`, rotation
+    in the (h, w) plane up to `max_angle` DEGREES, sub-voxel shift up to the `max_shift` fraction of each extent, brightness up to
+    +-`max_brightness`, contrast up to a factor `max_contrast`; the SG_AUGF_* bits).  One probability gates all of them.  mode
+    'none' (default: no launch is added anywhere), 'fixed' (p a host float) or 'ada' (p a one-element
     DEVICE float that sg_ada_update moves by `delta` every `interval` calls, towards the sign statistic of D's real-sample logits
     meeting `target`)."""
 
     def __init__(self, mode='none', ops=0, max_shift=0.125, fill=0.0, p=0.0, interval=4, target=0.6, delta=0.0, p_max=0.8,
-                 device=None):
+                 device=None, max_scale=1.25, max_angle=180.0, max_brightness=0.2, max_contrast=1.5):
         if mode not in ('none', 'fixed', 'ada'):
             raise ValueError(f'unknown augmentation mode {mode!r}')
         self.mode, self.ops, self.max_shift, self.fill = mode, int(ops), float(max_shift), float(fill)
+        self.max_scale, self.max_angle = float(max_scale), float(max_angle)
+        self.max_brightness, self.max_contrast = float(max_brightness), float(max_contrast)
         self.interval, self.delta, self.p_max = int(interval), float(delta), float(p_max)
         self.target = (int(round(float(target) * 1000000)), 1000000)
         self.state = None
@@ -66,6 +69,14 @@ class AugmentConfig:
     def max_shifts(self, x):
         """Largest shift per axis: the configured fraction of each extent of the [N,C,D,H,W] batch, rounded down."""
         return tuple(int(self.max_shift * e) for e in x.shape[2:])
+
+    def affine_draw(self, x, seed, offset, bump):
+        """The affine pass's parameter rows for the [N,C,D,H,W] batch x (its continuous shift: the fraction, not rounded)."""
+        return F.augment_affine_draw(x.shape[0], self.ops & F.AUGF_ALL, x.shape[2:], self.p, seed, offset=offset,
+                                     max_scale=self.max_scale, max_angle=math.radians(self.max_angle),
+                                     max_shift=tuple(self.max_shift * e for e in x.shape[2:]),
+                                     max_brightness=self.max_brightness, max_contrast=self.max_contrast, device=x.device,
+                                     bump=bump)
 
     def update(self, disc_real):
         if self.mode == 'ada':
@@ -84,6 +95,22 @@ def set_augment(cfg=None):
 
 def _augment(rng, x, tag):
     return rng.augment(x, tag) if _AUGMENT['cfg'].on else x
+
+
+def _draw_and_augment(cfg, x, seed, offset):
+    """The blitting pass, if a blitting bit is set (or no affine bit is: the launches of a configuration without the affine
+    family are what they were before it existed), then the affine pass, if an affine bit is set.  Both draws read the same
+    offset -- a host int, or the device counter, which the LAST draw launched advances: once per call either way."""
+    blit, affine = cfg.ops & F.AUG_ALL, cfg.ops & F.AUGF_ALL
+    rows = None
+    if affine:
+        rows = cfg.affine_draw(x, seed, offset, 0 if blit else 1 << 40)
+    if blit or not affine:
+        params = F.augment_draw(x.shape[0], blit, cfg.max_shifts(x), cfg.p, seed, offset=offset, device=x.device)
+        x = F.augment(x, params, cfg.fill, blit)
+    if affine:
+        x = F.augment_affine(x, rows, cfg.fill)
+    return x
 
 
 _DEVICE_RANDOM = RandomSource      # (the class itself: tests substitute `RandomSource` with host-drawn variants)
@@ -114,12 +141,21 @@ class InjectedRandom(RandomSource):
         return F.lerp(x, noise.contiguous(memory_format=torch.channels_last_3d), 1.0, float(stddev))
 
     def augment(self, x, tag):
-        """keys aug_real / aug_fake: int [N, 8] parameter rows (functional.augment_draw's layout); absent: identity."""
+        """keys aug_real / aug_fake: int [N, 8] parameter rows (functional.augment_draw's layout); aug_real_affine /
+        aug_fake_affine: float [N, 16] rows (functional.augment_affine_draw's layout); absent: identity."""
         cfg = _AUGMENT['cfg']
-        params = self.t.get(tag)
-        if params is None:
-            params = torch.zeros(x.shape[0], 8, dtype=torch.int32)
-        return F.augment(x, params.to(x.device, torch.int32).contiguous(), cfg.fill, cfg.ops)
+        blit, affine = cfg.ops & F.AUG_ALL, cfg.ops & F.AUGF_ALL
+        if blit or not affine:
+            params = self.t.get(tag)
+            if params is None:
+                params = torch.zeros(x.shape[0], 8, dtype=torch.int32)
+            x = F.augment(x, params.to(x.device, torch.int32).contiguous(), cfg.fill, blit)
+        if affine:
+            rows = self.t.get(tag + '_affine')
+            if rows is None:
+                rows = torch.tensor([1.0, 0, 0, 0, 0, 1, 0, 0, 0, 0, 1, 0, 1, 0, 0, 0]).repeat(x.shape[0], 1)      # identity, a = 1
+            x = F.augment_affine(x, rows.to(x.device, torch.float32).contiguous(), cfg.fill)
+        return x
 
 
 class StaticRandom:
@@ -180,12 +216,9 @@ class StaticRandom:
         return F.add_noise(x, stddev, self.base.seed, offset=self.counter)
 
     def augment(self, x, tag):
-        cfg = _AUGMENT['cfg']
         if self.counting:
             self.aug_calls += 1
-        params = F.augment_draw(x.shape[0], cfg.ops, cfg.max_shifts(x), cfg.p, self.base.seed, offset=self.aug_counter,
-                                device=x.device)
-        return F.augment(x, params, cfg.fill, cfg.ops)
+        return _draw_and_augment(_AUGMENT['cfg'], x, self.base.seed, self.aug_counter)
 
     def after_replay(self):
         self.base.calls += self.noise_calls

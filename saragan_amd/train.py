@@ -48,7 +48,10 @@ def augment_config(args, device):
                            max_shift=getattr(args, 'augment_max_shift', 0.125), fill=getattr(args, 'augment_fill', 0.0),
                            p=getattr(args, 'augment_p', 0.0), interval=getattr(args, 'ada_interval', None) or 4,
                            target=getattr(args, 'ada_target', None) or 0.6, p_max=getattr(args, 'ada_p_max', None) or 0.8,
-                           device=device)
+                           device=device, max_scale=getattr(args, 'augment_max_scale', 1.25),
+                           max_angle=getattr(args, 'augment_max_angle', 180.0),
+                           max_brightness=getattr(args, 'augment_max_brightness', 0.2),
+                           max_contrast=getattr(args, 'augment_max_contrast', 1.5))
 
 
 def run_training(args, device=None, max_steps_per_phase=None, log_every=1):
