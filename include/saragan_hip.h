@@ -442,6 +442,29 @@ int sg_lamb_update(float* p, const float* m, const float* v, float* ema, int64_t
                    const float* lr_dev, const int32_t* skip, double b1, double b2, float eps, float decay, float ema_decay,
                    sg_stream_t st);
 
+/* ---- spectral normalisation (SURFGAN_3D/networks/ops.py:80-127), batched over the normalised weights of one network -----
+ * A weight is W = reshape(w, [R, C]), C = cout, a segment of the flat f32 parameter buffer p; u [C] is its persistent state.
+ * One refresh with `iteration` = k: k times { v = normalise(u W^T); u = normalise(v W) }, normalise(x) = x / sqrt(max(|x|^2,
+ * 1e-12)); then sigma = v W u^T and eff = W / sigma at the same offsets of the effective-weight buffer (eff != p).  sigma = 0
+ * is not protected against (as the reference).  The pull-back maps G = dL/d(eff) to dL/dW with u, v held constant, in place:
+ *   g = (g - <g, eff> v_r u_c) / sigma
+ * Table (DEVICE, built once per network):
+ *   segs   int64[nseg][SG_SPECTRAL_SEG_FIELDS] {start (a multiple of 4), R, C, first block, rows per block (1..SG_SEG_CHUNK),
+ *          offset of u in `u`, offset of v in `v`, offset of the column partials in `cols`}
+ *   blocks int32[nblocks][2] {segment, row block}: block b covers rows [rb*rpb, min(R, (rb+1)*rpb)) of its segment; a segment's
+ *          ceil(R / rpb) blocks are consecutive, starting at its `first block`.
+ * Workspaces (f32): sigma[nseg], nt[nseg], partials[nblocks], cols[collen] with ceil(R / rpb) * C elements per segment; v[vlen]
+ * holds R elements per segment, u[ulen] C.  Padding between segments is neither read nor written.  A segment that does not
+ * fit its buffers is left alone as a whole.  sg_spectral_refresh is 2*iteration + 1 launches and sg_spectral_pullback two,
+ * whatever nseg; partial sums are combined in an order fixed by the table (no atomics): equal inputs give equal bits. */
+#define SG_SPECTRAL_SEG_FIELDS 8
+int sg_spectral_refresh(const float* p, float* eff, int64_t total, const int64_t* segs, const int32_t* blocks, int32_t nseg,
+                        int32_t nblocks, float* u, int64_t ulen, float* v, int64_t vlen, float* sigma, float* nt,
+                        float* partials, float* cols, int64_t collen, int32_t iteration, sg_stream_t st);
+int sg_spectral_pullback(float* g, const float* eff, int64_t total, const int64_t* segs, const int32_t* blocks, int32_t nseg,
+                         int32_t nblocks, const float* u, int64_t ulen, const float* v, int64_t vlen, const float* sigma,
+                         float* partials, sg_stream_t st);
+
 /* ---- discriminator augmentation with adaptive probability (Karras et al. 2020; not in the reference) ------------------
  * Pixel-blitting transforms only -- axis flips, 90-degree rotations in the (h, w) plane, integer translations with a constant
  * fill: index gathers, so values are copied bit for bit and the adjoint is another gather.  Per-sample parameters live in

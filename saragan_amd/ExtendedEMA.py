@@ -72,6 +72,7 @@ class ExtendedEMA:
                 flat = self._flat(prefix)
                 self._backup[prefix] = flat['param'].clone()
                 flat['param'].copy_(self.shadow_flat(prefix))
+            self.store.mark_rewritten()
             # the parameters alias the flat buffer (p.data = flat[...]): writing it moves neither data_ptr nor the version
             # counter the packed weight images are keyed by -- every writer of flat['param'] says so itself
             F.mark_packs_stale()
@@ -81,6 +82,7 @@ class ExtendedEMA:
         def run():
             for prefix in ('generator/', 'discriminator/'):
                 self._flat(prefix)['param'].copy_(self._backup[prefix])
+            self.store.mark_rewritten()
             F.mark_packs_stale()
         return Op(run, 'restore_original_weights')
 
@@ -89,5 +91,6 @@ class ExtendedEMA:
         def run():
             for prefix in ('generator/', 'discriminator/'):
                 self._flat(prefix)['param'].copy_(self.shadow_flat(prefix))
+            self.store.mark_rewritten()
             F.mark_packs_stale()
         return Op(run, 'ema_update_weights')

@@ -123,6 +123,8 @@ SIGNATURES = {
     'sg_lamb_ratios': (C.c_int, [_p, _i32, _i32, _p, _p, _p, _i32, _p, _p]),
     'sg_lamb_update': (C.c_int, [_p, _p, _p, _p, _i64, _p, _p, _i32, _i32, _p, _p, _f, _p, _p, C.c_double, C.c_double, _f, _f,
                                  _f, _p]),
+    'sg_spectral_refresh': (C.c_int, [_p, _p, _i64, _p, _p, _i32, _i32, _p, _i64, _p, _i64, _p, _p, _p, _p, _i64, _i32, _p]),
+    'sg_spectral_pullback': (C.c_int, [_p, _p, _i64, _p, _p, _i32, _i32, _p, _i64, _p, _i64, _p, _p, _p]),
     'sg_augment_draw': (C.c_int, [_p, _i32, C.c_uint32, _i32, _i32, _i32, _f, _p, _u64, _u64, _p, _u64, _p]),
     'sg_augment_apply': (C.c_int, [_p, _p, _p, _i32, _i32, _i32, _i32, _i32, C.c_uint32, _f, _i32, C.c_int, _p]),
     'sg_ada_update': (C.c_int, [_p, _i32, _p, _p, _i32, _i64, _i64, _f, _f, _p]),

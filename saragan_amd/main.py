@@ -107,6 +107,12 @@ def build_parser():
                         'an adjustment moves p by batch * interval / (ada_kimg * 1000)')
     p.add_argument('--ada_p_max', type=float, default=None,
                    help='(not in the reference) --augment ada: upper limit of p (default 0.8)')
+    p.add_argument('--d_spectral_norm', default=False, action='store_true',
+                   help='(not in the reference\'s flags; its networks/ops.py:80-127 defines the operation) spectral normalisation of '
+                        'every discriminator weight -- conv, from_rgb, dense -- by batched on-device power iteration: DESIGN.md '
+                        'section 4.2')
+    p.add_argument('--sn_iterations', type=int, default=1,
+                   help='(not in the reference) with --d_spectral_norm: power iterations per refresh (default 1)')
     p.add_argument('--ema_beta', type=float, default=0.99)
     p.add_argument('--noise_stddev', type=float, required=True)
     p.add_argument('--optimizer', type=none_or_str, choices=[None, 'Adam', 'SGD', 'Momentum', 'Adadelta', 'LAMB', 'AdamW'], default='Adam')
@@ -200,6 +206,13 @@ def finalize_args(args):
         if args.max_consecutive_nonfinite < 1:
             raise SystemExit('--max_consecutive_nonfinite must be >= 1')
     finalize_augment_args(args)
+    if getattr(args, 'sn_iterations', 1) != 1 and not getattr(args, 'd_spectral_norm', False):
+        raise SystemExit('--sn_iterations needs --d_spectral_norm')
+    if getattr(args, 'sn_iterations', 1) < 1:
+        raise SystemExit('--sn_iterations must be >= 1')
+    if getattr(args, 'd_spectral_norm', False) and getattr(args, 'use_adasum', False):
+        raise SystemExit('--d_spectral_norm does not support --use_adasum (the ranks\' raw weights differ between the local step '
+                         'and the combination): use the Average reduction')
     if not args.d_use_different_optimizer:
         args.d_optimizer = args.optimizer
     if not args.d_use_different_beta1:

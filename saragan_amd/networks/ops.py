@@ -206,14 +206,43 @@ class ScaledWeight:
         return self.var.shape
 
 
+_SPECTRAL = {'prefixes': (), 'iterations': 1}
+
+
+def set_spectral_norm(prefixes=(), iterations=1):
+    """(Not in the reference, whose conv3d / dense have no such argument.)  Every weight that get_weight creates under a scope
+    starting with one of `prefixes` -- conv, from_rgb, dense_1, dense_2 -- is spectrally normalised, with `iterations` power
+    iterations per refresh; () turns it off.  Set it before optimize_step builds a phase's step graph.  Returns the previous
+    (prefixes, iterations)."""
+    prefixes = (prefixes,) if isinstance(prefixes, str) else tuple(prefixes or ())
+    if int(iterations) < 1:
+        raise ValueError('set_spectral_norm: iterations >= 1')
+    for p in prefixes:
+        if not p.startswith('discriminator/'):
+            raise ValueError(f'spectral normalisation is offered for the discriminator only, got the scope prefix {p!r}')
+    prev = (_SPECTRAL['prefixes'], _SPECTRAL['iterations'])
+    _SPECTRAL['prefixes'], _SPECTRAL['iterations'] = prefixes, int(iterations)
+    return prev
+
+
+def spectral_norm_settings():
+    return _SPECTRAL['prefixes'], _SPECTRAL['iterations']
+
+
+def spectral_norm_applies(name):
+    """Whether the variable `name` is a weight that the module switch normalises."""
+    return name.endswith('/weight') and any(name.startswith(p) for p in _SPECTRAL['prefixes'])
+
+
 def get_weight(shape, activation, lrmul=1, use_eq_lr=True, use_spectral_norm=False, param=None):
-    """networks/ops.py:111-127."""
+    """networks/ops.py:111-127.  With use_spectral_norm (or under a scope that set_spectral_norm names) the weight is
+    registered as normalised and the networks read W / sigma from its effective-weight leaf (varstore.VariableStore.normalise;
+    refreshed by the step graph, optimization.StepGraph): W / sigma does not change with the scalar the reference multiplies
+    in before it normalises (ops.py:121-124), so the coefficient is 1."""
     fan_in = np.prod(shape[:-1])
     gain = calculate_gain(activation, param)
     he_std = gain / np.sqrt(fan_in)
     runtime_coef = he_std * lrmul
-    if use_spectral_norm:
-        raise NotImplementedError('spectral_norm is not used by the pgan path')
     from ..varstore import current_store, scope_name
     full = (scope_name() + '/weight') if scope_name() else 'weight'
     fresh = full not in current_store().vars
@@ -221,6 +250,9 @@ def get_weight(shape, activation, lrmul=1, use_eq_lr=True, use_spectral_norm=Fal
     if fresh and lrmul != 1:      # init_std = 1 / lrmul (ops.py:115,118-119); the coefficient below carries lrmul back in
         with torch.no_grad():
             w.mul_(1.0 / lrmul)
+    if use_spectral_norm or spectral_norm_applies(full) or full in current_store().effective:
+        current_store().normalise(full)      # (refuses weights outside the discriminator, and a network that is flat already)
+        return ScaledWeight(current_store().effective_weight(full), 1.0)      # (refuses values that are not current)
     return ScaledWeight(w, runtime_coef if use_eq_lr else 1.0)
 
 
@@ -424,7 +456,14 @@ def _unsupported(name):
     return f
 
 
-spectral_norm = _unsupported('spectral_norm')
+def spectral_norm(w, iteration=1):
+    """networks/ops.py:80-108 on an arbitrary tensor.  Not offered: the normalisation here is a property of a stored weight
+    (its state u lives in the variable store, its value in the network's effective-weight buffer)."""
+    raise NotImplementedError('networks.ops.spectral_norm on a free tensor is not supported: create the weight with '
+                              'get_weight(..., use_spectral_norm=True) or turn the layers\' normalisation on with '
+                              'set_spectral_norm(prefixes=(\'discriminator/\',))')
+
+
 group_conv3d = _unsupported('group_conv3d')
 instance_norm = _unsupported('instance_norm')
 apply_noise = _unsupported('apply_noise')

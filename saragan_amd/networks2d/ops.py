@@ -28,6 +28,13 @@ def conv2d(x, fmaps, kernel, activation, param=None, lrmul=1):
     xin, in_info = _consume(as_volume(x), premask=True)
     xin = as_volume(xin)
     kh, kw = kernel
+    from ..networks.ops import spectral_norm_applies
+    from ..varstore import current_store, scope_name
+    full = (scope_name() + '/weight') if scope_name() else 'weight'
+    if spectral_norm_applies(full) or full in current_store().effective:
+        # the 2-D layers hand a VIEW of the filter to the kernels, whose gradient would not land in the raw weight's slot
+        # (every 2-D network reaches its dense layers through a conv2d: refused here, before anything is registered)
+        raise NotImplementedError('spectral normalisation (networks.ops.set_spectral_norm) is not offered for the 2-D networks')
     w = get_weight([kh, kw, xin.shape[1], fmaps], activation, param=param, lrmul=lrmul)
     if xin.dtype != compute_dtype():
         xin, in_info = xin.to(compute_dtype()), None

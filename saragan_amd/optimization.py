@@ -378,7 +378,42 @@ class StepGraph:
     def add_train(self, net, optimizer, names, clipping):
         self.trains.append(dict(net=net, optimizer=optimizer, names=names, clipping=bool(clipping)))
         self._refuse_guard_with_adasum()
+        self._refuse_spectral_with_adasum()
         return len(self.trains) - 1
+
+    # -- spectral normalisation (not used by the reference's pgan; networks.ops.set_spectral_norm) ----------------------------
+    def _refuse_spectral_with_adasum(self):
+        for t in self.trains:
+            if getattr(t['optimizer'].distributed, 'delta_form', False) and \
+                    any(n in self.store.effective for n in t['names']):
+                # Adasum combines the ranks' LOCAL weight deltas: their raw weights differ between the local step and the
+                # combination, and so would u and the effective weights.  Refused rather than half-supported.
+                raise ValueError('spectral normalisation does not support Adasum (--use_adasum): use the Average reduction '
+                                 'or turn --d_spectral_norm off')
+
+    def _refresh_effective(self, force=False):
+        """Before a discriminator forward: W / sigma of the normalised weights -- a fixed number of launches on the current
+        stream, eager or captured; every discriminator pass up to the next refresh shares the result.  A `simultaneous` step
+        refreshes if the raw weights were rewritten since the last refresh (the optimiser step, a restore, a hand-off: every
+        step of a training loop); an `alternate` step always does two, before forward_discriminator and before
+        forward_generator."""
+        if self.store.effective:
+            self.store.refresh_effective('discriminator/', self.cfg.get('sn_iterations', 1), force=force)
+
+    def _pull_back(self, info):
+        """The flat buffer holds the gradient with respect to the effective weights in the raw weights' own slots: mapped in
+        place to the gradient with respect to the raw weights (two launches).  Linear in the gradient with the same W / sigma,
+        u, v, sigma on every rank: it commutes with the all-reduce sum and with gscale."""
+        flat = info['flat']
+        if flat.get('spectral') is not None and any(n in self.store.effective for n in info['names']):
+            # the launches cover every normalised layer of the network: the slots of those outside this train op (frozen while
+            # mixing) are cleared first, or what another train op left there would be divided by sigma again every step
+            mine = set(info['names'])
+            for n in flat['normalised']:
+                if n not in mine:
+                    o, cnt = flat['offsets'][n]
+                    flat['grad'][o:o + cnt].zero_()
+            F.spectral_pullback_(flat['spectral'], flat['grad'], flat['eff'])
 
     # -- non-finite step guard ------------------------------------------------------------------------------------------
     def configure_guard(self, on=True, max_consecutive=None):
@@ -471,6 +506,7 @@ class StepGraph:
                                         kernel_spec=c['kernel_spec'], filter_spec=c['filter_spec'], param=c['leakiness'])
             return [sample.detach() for _ in fetches]
         self._stepped = True
+        self._refuse_spectral_with_adasum()
         if self.guard is not None:
             self._refuse_guard_with_adasum()
             self.guard.prepare(self, real.device)
@@ -516,11 +552,13 @@ class StepGraph:
         lr_dev = lr_dev or {}
         d_ids = [t for t in train_ids if self.trains[t]['net'] == 'discriminator']
         g_ids = [t for t in train_ids if self.trains[t]['net'] == 'generator']
+        self._refresh_effective(force=True)
         disc_loss, gp_loss = forward_discriminator(c['generator'], c['discriminator'], real, *net_args,
                                                    c['gp_weight'], c['noise_stddev'])
         out.update(disc_loss=disc_loss, gp_loss=gp_loss)
         for tid in d_ids:
             self._finish(tid, self._backward(tid, out), out, apply=tid in want_train, lr_dev=lr_dev.get(tid), marks=marks)
+        self._refresh_effective(force=True)      # (the updated discriminator)
         gen_sample, gen_loss = forward_generator(c['generator'], c['discriminator'], real, *net_args,
                                                  c['noise_stddev'], is_reuse=True)
         out.update(gen_sample=gen_sample, gen_loss=gen_loss)
@@ -531,6 +569,7 @@ class StepGraph:
         """Forward pass and both backward passes of a 'simultaneous' step (no optimizer): fills `out`, returns the per-net
         records `_finish` needs.  between(j): called between backward pass j and j + 1 (the segmented capture cuts there)."""
         c = self.cfg
+        self._refresh_effective()
         nets = {self.trains[t]['net'] for t in train_ids}
         if nets >= {'generator', 'discriminator'}:
             with linear_generator_link():   # wgan: G's gradient through D comes out of D's own backward
@@ -609,7 +648,8 @@ class StepGraph:
         norms = tuple(sorted(t for t in train_ids if ('max_norm', t) in self._wanted))
         dist_ids = tuple(t for t in train_ids if self.trains[t]['optimizer'].distributed is not None)
         key = (tuple(train_ids), tuple(sorted(want_train)), norms, alpha_class, tuple(real.shape), str(compute_dtype()), strategy,
-               self.guard is not None)
+               self.guard is not None,
+               strategy == 'simultaneous' and 'discriminator/' in self.store.rewritten)      # (a pending refresh is baked in)
         caps = self.__dict__.setdefault('_captures', {})
         ent = caps.get(key)
         if ent is None:
@@ -701,8 +741,8 @@ class StepGraph:
             F.mark_packs_stale()
             marks = []
             try:
-                self.assert_no_live_accumulate_grad([p for _, p in self.store.trainable('generator/')] +
-                                                    [p for _, p in self.store.trainable('discriminator/')])
+                self.assert_no_live_accumulate_grad(self.store.grad_leaves('generator/') +
+                                                    self.store.grad_leaves('discriminator/'))
                 torch.cuda.synchronize()
                 pool = self.__dict__.get('_cap_pool')
                 if pool is None:
@@ -760,6 +800,7 @@ class StepGraph:
                 L.set_random_source(base)
                 F.mark_packs_stale()      # (a capture records launches without running them)
             ent['rnd'].counting = False
+            ent['rewritten'] = set(self.store.rewritten)      # (what a step of this kind leaves pending: repeated by a replay)
             ent['packs'] = F.live_packs()      # the graph reads (and refreshes) these images: they live as long as it does
             ent['marks'] = marks
             # replays need the captured launches and the output buffers, not the Python autograd graph: without it the
@@ -791,20 +832,21 @@ class StepGraph:
                 if log is not None:
                     log.append(('segment', k))
                 if info['dist'] is not None:
-                    info['dist'].begin(info['flat']['grad'], info['ranges'], [self.store.vars[n] for n in info['names']], None)
+                    info['dist'].begin(info['flat']['grad'], info['ranges'], [self.store.stand_in(n) for n in info['names']], None)
                     nb = info['dist'].launch_all()
                     if log is not None:
                         log.append(('buckets', k, tid, nb))
         else:
             ent['graph'].replay()
         F.mark_packs_stale()                   # (the graph's optimiser launches rewrote the parameters)
+        self.store.rewritten = set(ent['rewritten'])
         ent['rnd'].after_replay()
         out = dict(ent['out'])
         out['__static__'] = True
         if dist_ids:       # the waits and the optimiser launches follow eagerly
             for tid, info in ent['pend']:
                 if info['dist'] is not None and 'segments' not in ent:
-                    info['dist'].begin(info['flat']['grad'], info['ranges'], [self.store.vars[n] for n in info['names']], None)
+                    info['dist'].begin(info['flat']['grad'], info['ranges'], [self.store.stand_in(n) for n in info['names']], None)
                 self._finish(tid, info, out, apply=tid in want_train)
         elif self.ema is not None:
             for prefix, ranges in ent['marks']:
@@ -819,11 +861,15 @@ class StepGraph:
         ranges = self._ranges(prefix, names)
         for (o, n) in ranges:
             flat['grad'][o:o + n].zero_()
-        params = [self.store.vars[n] for n in names]
+        # a normalised weight's effective leaf stands in for the raw parameter: the networks read it, and its gradient lands in
+        # the raw parameter's own slot (same shape), where _finish pulls it back to the raw weight
+        params = [self.store.stand_in(n) for n in names]
         slots = {}
         for p, n in zip(params, names):      # .grad views may have been replaced by autograd: re-point them
             o, cnt = flat['offsets'][n]
             p.grad = slots[id(p)] = flat['grad'][o:o + cnt].view(p.shape)
+            if p is not self.store.vars[n]:
+                self.store.vars[n].grad = slots[id(p)]
         loss = out['gen_loss'] if tr['net'] == 'generator' else out['disc_loss']
         dist = tr['optimizer'].distributed
         other = 'discriminator/' if tr['net'] == 'generator' else 'generator/'
@@ -837,7 +883,7 @@ class StepGraph:
         for p in params:
             p.grad = None
         with F.grads_into({p.data_ptr(): slots[id(p)] for p in params}), \
-                F.skip_param_grads(p for _, p in self.store.trainable(other)):   # e.g. D's weights under the G loss
+                F.skip_param_grads(self.store.grad_leaves(other)):   # e.g. D's weights under the G loss
             if link is None:
                 torch.autograd.backward(loss, inputs=params, retain_graph=retain)
             elif tr['net'] == 'discriminator':   # also deliver d disc_loss / d fake for the generator's backward
@@ -878,6 +924,7 @@ class StepGraph:
         if info['dist'] is not None:
             info['dist'].finish()              # waits for the bucketed reductions
             gscale = info['dist'].grad_scale   # 1 / world after a SUM (the average is folded into the update kernel)
+        self._pull_back(info)
         norms = tr['clipping'] or ('max_norm', tid) in self._wanted
         guard = None
         if apply and self.guard is not None:
@@ -924,6 +971,7 @@ class StepGraph:
                 tr['optimizer'].apply(info['prefix'], flat, ranges, gscale, ema_flat, ema_decay, lr_dev=lr_dev)
             else:
                 tr['optimizer'].apply(info['prefix'], flat, ranges, gscale, ema_flat, ema_decay)
+            self.store.mark_rewritten(info['prefix'])
             if self.ema is not None:
                 self.ema.mark_updated(info['prefix'], ranges)
                 if marks is not None:       # a replay repeats this bookkeeping (ExtendedEMA.apply skips the covered ranges)
@@ -953,8 +1001,12 @@ def optimize_step(optimizer_gen, optimizer_disc, generator, discriminator, real_
     shapes = plan(phase, base_shape, latent_dim, kernel_spec, filter_spec)
     for name, shp in shapes.items():           # create in the reference's order (weights N(0,1), biases 0)
         store.get(name, shp, 'normal' if name.endswith('weight') else 'zeros')
+    from .networks import ops as nops
+    for name in shapes:                        # (not in the reference) the weights networks.ops.set_spectral_norm names
+        if nops.spectral_norm_applies(name):
+            store.normalise(name)
     freeze_names = None if freeze_vars is None else [_key(v) for v in freeze_vars]
-    cfg = dict(generator=generator, discriminator=discriminator, latent_dim=latent_dim, alpha=alpha, phase=phase,
+    cfg = dict(sn_iterations=nops.spectral_norm_settings()[1], generator=generator, discriminator=discriminator, latent_dim=latent_dim, alpha=alpha, phase=phase,
                base_shape=base_shape, kernel_spec=kernel_spec, filter_spec=filter_spec, activation=activation,
                leakiness=leakiness, loss_fn=loss_fn, gp_weight=gp_weight, optim_strategy=optim_strategy,
                noise_stddev=noise_stddev, freeze_names=freeze_names, placeholder=real_image_input)

@@ -381,8 +381,15 @@ def broadcast_global_variables(store, root_rank=0, group=None):
     for prefix, flat in store.flat.items():
         dist.broadcast(flat['param'], src=root_rank, group=group)
         done.update(flat['offsets'].keys())
+        if flat.get('spectral') is not None:      # spectral normalisation's state: equal u keeps the ranks' effective weights equal
+            dist.broadcast(flat['spectral'].u, src=root_rank, group=group)
+            done.update(store.u_name(k) for k in flat['normalised'])
     for k, v in store.vars.items():
         if k not in done:
             dist.broadcast(v.data, src=root_rank, group=group)
+    for k, v in store.state.items():
+        if k not in done:
+            dist.broadcast(v, src=root_rank, group=group)
+    store.mark_rewritten()
     from . import functional as F
     F.mark_packs_stale()      # the flat buffers were rewritten behind the version counters the packed weight images are keyed by

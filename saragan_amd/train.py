@@ -57,10 +57,13 @@ def augment_config(args, device):
 def run_training(args, device=None, max_steps_per_phase=None, log_every=1):
     """optuna_objective(trial=None, args, config).  Returns a dict with per-phase statistics."""
     prev_augment = L.set_augment(None)      # (_run_training installs the run's own; the caller's comes back afterwards)
+    on = bool(getattr(args, 'd_spectral_norm', False))      # (not in the reference's flags) --d_spectral_norm / --sn_iterations
+    prev_spectral = nops.set_spectral_norm(('discriminator/',) if on else (), getattr(args, 'sn_iterations', 1) if on else 1)
     try:
         return _run_training(args, device, max_steps_per_phase, log_every)
     finally:
         L.set_augment(prev_augment)
+        nops.set_spectral_norm(*prev_spectral)
 
 
 def _run_training(args, device, max_steps_per_phase, log_every):

@@ -88,8 +88,10 @@ def print_summary_to_stdout(global_step, in_phase_step, img_s, local_img_s, d_lo
 
 # ---- checkpoints: {tf variable name: ndarray}, the contract of tf.train.Saver(var_list) ---------------------
 def save_checkpoint(store, path):
-    """tf.train.Saver(var_list).save(sess, path): trainable G+D variables only (no optimiser slots, no EMA)."""
+    """tf.train.Saver(var_list).save(sess, path): trainable G+D variables (no optimiser slots, no EMA) and the store's
+    non-trainable state (spectral normalisation's u, which the reference's tf.global_variables saver would hold too)."""
     arrs = {k: v.detach().float().cpu().numpy() for k, v in store.vars.items()}
+    arrs.update((k, v.detach().float().cpu().numpy()) for k, v in store.state.items())
     os.makedirs(os.path.dirname(os.path.abspath(path)), exist_ok=True)
     np.savez(path if path.endswith('.npz') else path + '.npz', **arrs)
 
@@ -118,6 +120,10 @@ def restore_variables(store, phase, starting_phase, logdir, continue_path, var_l
         for n in names:
             if n in store.vars:
                 store.vars[n].copy_(torch.as_tensor(sd[n]).to(store.vars[n].device).reshape(store.vars[n].shape))
+                u = store.u_name(n)      # the state of a normalised weight travels with it; a checkpoint without it: fresh u
+                if n in store.effective and u in sd:
+                    store.state[u].copy_(torch.as_tensor(sd[u]).to(store.state[u].device).reshape(store.state[u].shape))
+    store.mark_rewritten()
     if ema is not None:
         ema.reset_to_variables()
     if verbose:
