@@ -358,6 +358,36 @@ int sg_minibatch_stddev_fwd(const void* x, void* y, float* workspace, int32_t n,
 /* Its gradient: dx[n,d,h,w,c] from dy[n,d,h,w,c+1] and the forward input x (same workspace size). */
 int sg_minibatch_stddev_bwd(const void* dy, const void* x, void* dx, float* workspace, int32_t n,
                             int64_t vox_per_sample, int32_t c, int32_t group_size, sg_dtype dt, sg_stream_t st);
+/* Minibatch standard deviation as a per-sample statistic, twice differentiable (csrc/mbstd.hip).  The batch is
+ * `nseg` consecutive sub-batches of n / nseg samples; inside each, G = min(group_size, n / nseg), M = (n / nseg) / G and group m
+ * holds the samples g * M + m (the reshape of networks/ops.py:317).  P = c * vox_per_sample; per position i of a group:
+ * mu_i the group mean, d_gi = x_gi - mu_i, sigma_i = sqrt(mean_g d_gi^2 + 1e-8).  x is NDHWC (any c, any alignment), all
+ * arithmetic f32, every sum in a fixed order (no float atomics).  SG_EINVAL before any launch: a NULL pointer, n % nseg != 0,
+ * (n / nseg) % G != 0, a workspace smaller than sg_mbstd_stat_workspace().
+ *   fwd  (2 launches): stat[n] (f32, every sample of a group holds the same value) = (1/P) sum_i sigma_i
+ *   bwd  (1 launch):   dx_gi = S / (P G) * d_gi / sigma_i,  S = sum of gstat over the group's samples
+ *   bwd2 (<= 2 launches): h the cotangent of dx (shaped and typed like x);
+ *        ggstat[n] (f32, per sample of the group) = (1 / (P G)) sum_{g,i} h_gi d_gi / sigma_i
+ *        gx_gi = S / (P G) * [(h_gi - hbar_i) / sigma_i - d_gi (sum_g' h_g'i d_g'i) / (G sigma_i^3)],  hbar_i = mean_g h_gi
+ *        gx or ggstat may be NULL (not both): that output is not computed. */
+size_t sg_mbstd_stat_workspace(int32_t n, int64_t vox_per_sample, int32_t c, int32_t group_size, int32_t nseg);
+int sg_mbstd_stat_fwd(const void* x, float* stat, float* workspace, size_t workspace_bytes, int32_t n, int64_t vox_per_sample,
+                      int32_t c, int32_t group_size, int32_t nseg, sg_dtype dt, sg_stream_t st);
+int sg_mbstd_stat_bwd(const float* gstat, const void* x, void* dx, int32_t n, int64_t vox_per_sample, int32_t c,
+                      int32_t group_size, int32_t nseg, sg_dtype dt, sg_stream_t st);
+int sg_mbstd_stat_bwd2(const void* h, const void* x, const float* gstat, void* gx, float* ggstat, float* workspace,
+                       size_t workspace_bytes, int32_t n, int64_t vox_per_sample, int32_t c, int32_t group_size, int32_t nseg,
+                       sg_dtype dt, sg_stream_t st);
+/* The rank-1 term a per-sample constant channel adds to the SAME-padded convolution after it: with B f32 [plane]
+ * (plane = voxels * cout of the convolution's output, NDHWC order) and s f32 [n], one launch each:
+ *   term_fwd:   out[n][j] = y[n][j] + s[n] * B[j]   (f32 add, one rounding to dt; y NULL: the outer product alone)
+ *   term_dot:   r[n] = sum_j g[n][j] * B[j]          (f32)
+ *   term_outer: Bg[j] = sum_n s[n] * g[n][j]         (f32, n ascending)
+ * Each one's derivatives are the other two. */
+int sg_mbstd_term_fwd(const void* y, const float* s, const float* B, void* out, int32_t n, int64_t plane, sg_dtype dt,
+                      sg_stream_t st);
+int sg_mbstd_term_dot(const void* g, const float* B, float* r, int32_t n, int64_t plane, sg_dtype dt, sg_stream_t st);
+int sg_mbstd_term_outer(const float* s, const void* g, float* Bg, int32_t n, int64_t plane, sg_dtype dt, sg_stream_t st);
 /* dtype conversion between f32 and bf16 buffers (dst dtype = dt_dst). */
 int sg_cast(const void* src, sg_dtype dt_src, void* dst, sg_dtype dt_dst, int64_t numel, sg_stream_t st);
 

@@ -106,6 +106,13 @@ SIGNATURES = {
     'sg_sumsq_ndhwc_keep_w': (C.c_int, [_p, _p, _i32, _i32, _i32, _i32, _i32, C.c_int, _p]),
     'sg_minibatch_stddev_fwd': (C.c_int, [_p, _p, _p, _i32, _i64, _i32, _i32, C.c_int, _p]),
     'sg_minibatch_stddev_bwd': (C.c_int, [_p, _p, _p, _p, _i32, _i64, _i32, _i32, C.c_int, _p]),
+    'sg_mbstd_stat_workspace': (_sz, [_i32, _i64, _i32, _i32, _i32]),
+    'sg_mbstd_stat_fwd': (C.c_int, [_p, _p, _p, _sz, _i32, _i64, _i32, _i32, _i32, C.c_int, _p]),
+    'sg_mbstd_stat_bwd': (C.c_int, [_p, _p, _p, _i32, _i64, _i32, _i32, _i32, C.c_int, _p]),
+    'sg_mbstd_stat_bwd2': (C.c_int, [_p, _p, _p, _p, _p, _p, _sz, _i32, _i64, _i32, _i32, _i32, C.c_int, _p]),
+    'sg_mbstd_term_fwd': (C.c_int, [_p, _p, _p, _p, _i32, _i64, C.c_int, _p]),
+    'sg_mbstd_term_dot': (C.c_int, [_p, _p, _p, _i32, _i64, C.c_int, _p]),
+    'sg_mbstd_term_outer': (C.c_int, [_p, _p, _p, _i32, _i64, C.c_int, _p]),
     'sg_cast': (C.c_int, [_p, C.c_int, _p, C.c_int, _i64, _p]),
     'sg_adam_ema': (C.c_int, [_p, _p, _p, _p, _p, _i64, _f, _f, _f, _f, _f, _f, _p]),
     'sg_optim_step': (C.c_int, [C.c_int, _p, _p, _p, _p, _p, _i64, _f, _f, _f, C.c_int, _f, _f, _p]),

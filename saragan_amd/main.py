@@ -113,6 +113,11 @@ def build_parser():
                         'section 4.2')
     p.add_argument('--sn_iterations', type=int, default=1,
                    help='(not in the reference) with --d_spectral_norm: power iterations per refresh (default 1)')
+    p.add_argument('--d_mbstd_group', type=int, default=0,
+                   help='(not in the reference, whose pgan/discriminator.py:50 is commented out) minibatch standard deviation in '
+                        'front of the discriminator\'s last convolution, over groups of this many samples (0 = off; pgan only). '
+                        'Groups are local to a rank: they are formed inside each process\'s own batch, which the group size must '
+                        'divide in every phase, and never span ranks.  DESIGN.md section 4.3')
     p.add_argument('--ema_beta', type=float, default=0.99)
     p.add_argument('--noise_stddev', type=float, required=True)
     p.add_argument('--optimizer', type=none_or_str, choices=[None, 'Adam', 'SGD', 'Momentum', 'Adadelta', 'LAMB', 'AdamW'], default='Adam')
@@ -197,6 +202,34 @@ def finalize_augment_args(args):
     return args
 
 
+def phase_batch_size(args, phase, global_size=1):
+    """The per-process batch of a phase (optuna_objective.py:127-136; train._run_training computes the same)."""
+    batch_size = max(1, args.base_batch_size // (2 ** (phase - 1)))
+    if args.max_global_batch_size is not None and batch_size > args.max_global_batch_size / global_size:
+        batch_size = int(args.max_global_batch_size / global_size)
+    return batch_size
+
+
+def finalize_mbstd_args(args):
+    """--d_mbstd_group: refused at start-up where the run could not use it."""
+    group = getattr(args, 'd_mbstd_group', 0) or 0
+    if group < 0:
+        raise SystemExit('--d_mbstd_group must be >= 0 (0 turns the layer off)')
+    if group == 0:
+        return args
+    if args.architecture != 'pgan':
+        raise SystemExit(f'--d_mbstd_group is offered for the pgan architecture only, got {args.architecture!r}')
+    if getattr(args, 'base_batch_size', None):
+        import os
+        world = int(os.environ.get('WORLD_SIZE', '1')) if getattr(args, 'horovod', False) else 1
+        last = min(args.ending_phase, get_num_phases(args.start_shape, args.final_shape))
+        for phase in range(args.starting_phase, last + 1):
+            n = phase_batch_size(args, phase, world)
+            if n < 1 or n % min(group, n) != 0:
+                raise SystemExit(f'--d_mbstd_group {group} does not divide the per-process batch {n} of phase {phase}')
+    return args
+
+
 def finalize_args(args):
     """main.py:384-411 post-parse defaults: the discriminator inherits the generator's optimiser settings unless
     the --d_use_different_* switches are given; presets fill missing kernel/filter specs."""
@@ -206,6 +239,7 @@ def finalize_args(args):
         if args.max_consecutive_nonfinite < 1:
             raise SystemExit('--max_consecutive_nonfinite must be >= 1')
     finalize_augment_args(args)
+    finalize_mbstd_args(args)
     if getattr(args, 'sn_iterations', 1) != 1 and not getattr(args, 'd_spectral_norm', False):
         raise SystemExit('--sn_iterations needs --d_spectral_norm')
     if getattr(args, 'sn_iterations', 1) < 1:

@@ -10,6 +10,7 @@ import torch.nn.functional as TF
 
 from .. import functional as F
 from ..varstore import compute_dtype, current_store
+from .ops import mbstd_segments
 
 
 class RandomSource:
@@ -364,12 +365,14 @@ def forward_simultaneous(generator, discriminator, real_image_input, latent_dim,
     # variables (the edge into G is never followed), the G-loss gradient only w.r.t. G's (no D weight gradients).
     link = _LINK['on'] and loss_fn == 'wgan' and gen_sample_noisy.requires_grad
     if link and not _NO_BATCHED_D:
-        # The pgan discriminator has no op that couples batch samples (its minibatch-stddev layer is disabled,
-        # pgan/discriminator.py:50), so D(real) and D(fake) are ONE pass over the concatenated batch: a third fewer
-        # launches in D's forward and backward, twice the tiles for the low-resolution layers.
+        # The only op of the pgan discriminator that couples batch samples is the minibatch-stddev layer (off by default,
+        # pgan/discriminator.py:50; ops.set_minibatch_stddev), and told that the batch is two sub-batches it groups each on
+        # its own: D(real) and D(fake) are ONE pass over the concatenated batch: a third fewer launches in D's forward and
+        # backward, twice the tiles for the low-resolution layers.
         fake_in = gen_sample_noisy.detach().requires_grad_(True)
         n_real = real_image_input.shape[0]
-        both = discriminator(torch.cat([real_image_input, fake_in], dim=0), alpha, phase, **net).float()
+        with mbstd_segments(2):
+            both = discriminator(torch.cat([real_image_input, fake_in], dim=0), alpha, phase, **net).float()
         disc_real, disc_fake_g = both[:n_real], both[n_real:]
         disc_fake_d = disc_fake_g
     else:

@@ -426,6 +426,72 @@ def minibatch_stddev_layer(x, group_size=4):
     return F.minibatch_stddev(_val(x), group_size)
 
 
+_MBSTD = {'group': 0, 'segments': 1}
+
+
+def set_minibatch_stddev(group=0):
+    """(Not in the reference, whose line pgan/discriminator.py:50 is commented out.)  group > 0 puts minibatch_stddev_layer with
+    that group size in front of discriminator_out's convolution of the 3-D pgan discriminator (conv3d_minibatch_stddev below);
+    0 turns it off.  Set it before optimize_step builds a phase's step graph.  Returns the previous group."""
+    if int(group) < 0:
+        raise ValueError('set_minibatch_stddev: group >= 0 (0 turns the layer off)')
+    prev = _MBSTD['group']
+    _MBSTD['group'] = int(group)
+    return prev
+
+
+def minibatch_stddev_settings():
+    return _MBSTD['group']
+
+
+class mbstd_segments:
+    """Context for a discriminator pass over k concatenated sub-batches (loss.forward_simultaneous: real, then generated): the
+    layer's groups stay inside a sub-batch, so the pass computes what k separate passes compute."""
+
+    def __init__(self, k):
+        self.k = int(k)
+
+    def __enter__(self):
+        self.prev = _MBSTD['segments']
+        _MBSTD['segments'] = self.k
+
+    def __exit__(self, *a):
+        _MBSTD['segments'] = self.prev
+
+
+def conv3d_minibatch_stddev(x, fmaps, kernel, activation, param=None):
+    """act(apply_bias(conv3d(minibatch_stddev_layer(x), fmaps, kernel))) without the concatenated tensor: the statistic channel is
+    constant over a sample's voxels, so its share of the SAME-padded convolution is the rank-1 term s_n * B[pos, :] with
+    B[pos, :] = the sum of the statistic channel's filter over the taps in bounds at pos (functional.mbstd_term).
+    The C real channels keep the variable `weight` [*kernel, C, fmaps]; the statistic channel's filter is the variable
+    `mbstd/weight` [*kernel, 1, fmaps].  Both carry the equalised-LR coefficient of the full [*kernel, C + 1, fmaps] shape
+    (spectrally normalised: each on its own, coefficient 1)."""
+    from ..varstore import current_store, scope_name
+    group, nseg = _MBSTD['group'], _MBSTD['segments']
+    if len(x.shape) != 5:
+        raise NotImplementedError('minibatch stddev is offered for the 3-D pgan discriminator only')
+    xt = _consume(x, False)[0]       # the statistic reads x too, and its backward applies no LeakyReLU mask
+    cin = x.shape[1]
+    coef_full = calculate_gain(activation, param) / np.sqrt(np.prod(kernel) * (cin + 1))
+    s = F.mbstd_stat(xt, group, nseg)
+    lz = conv3d(x, fmaps, kernel, activation, param=param)
+    if (scope_name() + '/weight') not in current_store().effective:
+        lz.coef = coef_full
+    y = _val(lz)
+    with variable_scope('mbstd'):
+        wm = get_weight([*kernel, 1, fmaps], activation, param=param)
+        normalised = (scope_name() + '/weight') in current_store().effective
+    B = F.mbstd_plane(wm.var, 1.0 if normalised else coef_full, tuple(y.shape[2:]))
+    y = F.mbstd_term(y, s, B)
+    b = get_variable('bias', [fmaps], 'zeros')
+    if activation == 'leaky_relu':
+        assert param is not None
+        return F.bias_act(y, b, True, float(param))
+    if activation != 'linear':
+        raise ValueError(f"Unknown activation {activation}")
+    return F.bias_act(y, b, False, 0.0)
+
+
 _NO_LERP_PRUNE = bool(int(os.environ.get('SARAGAN_NO_LERP_PRUNE', '0')))   # diagnostic: alpha = 0 / 1 through sg_axpby
 
 

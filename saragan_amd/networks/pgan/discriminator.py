@@ -2,7 +2,8 @@
 error behaviour); the ops are saragan_amd.networks.ops (gfx950 kernels)."""
 from ..ops import *  # noqa: F401,F403
 from ..specs import filters, kernels
-from ..ops import act, apply_bias, conv3d, dense, downscale3d, from_rgb, lerp, materialize, variable_scope
+from ..ops import (act, apply_bias, conv3d, conv3d_minibatch_stddev, dense, downscale3d, from_rgb, lerp, materialize,
+                   minibatch_stddev_settings, variable_scope)
 
 
 def discriminator_block(x, activation, kernel_spec, filter_spec, i, param=None):
@@ -22,12 +23,17 @@ def discriminator_block(x, activation, kernel_spec, filter_spec, i, param=None):
 
 
 def discriminator_out(x, latent_dim, activation, kernel_spec, filter_spec, param):
-    """pgan/discriminator.py:48-68 (minibatch_stddev_layer stays disabled, :50)."""
+    """pgan/discriminator.py:48-68.  minibatch_stddev_layer (:50, commented out in the reference) stays disabled unless
+    ops.set_minibatch_stddev turned it on: then the first convolution is the reference's layer on concat(x, statistic),
+    evaluated without the concatenation (ops.conv3d_minibatch_stddev)."""
     with variable_scope('discriminator_out'):
         kernel = kernels(kernel_spec, 0, 1)
-        x = conv3d(x, filters(filter_spec, 0, 0), kernel, activation=activation, param=param)
-        x = apply_bias(x)
-        x = act(x, activation, param=param)
+        if minibatch_stddev_settings():
+            x = conv3d_minibatch_stddev(x, filters(filter_spec, 0, 0), kernel, activation, param=param)
+        else:
+            x = conv3d(x, filters(filter_spec, 0, 0), kernel, activation=activation, param=param)
+            x = apply_bias(x)
+            x = act(x, activation, param=param)
         with variable_scope('dense_1'):
             x = dense(x, latent_dim, activation=activation, param=param)
             x = apply_bias(x)

@@ -7,6 +7,9 @@ from collections import OrderedDict
 import numpy as np
 
 
+MBSTD_WEIGHT = 'discriminator_out/mbstd/weight'      # under 'discriminator/': exists only with networks.ops.set_minibatch_stddev on
+
+
 def _spec(spec, phase_i, layer_i):
     if phase_i >= len(spec) or layer_i >= len(spec[phase_i]):
         raise ValueError(f'no entry for phase {phase_i}, layer {layer_i} in the kernel/filter spec')
@@ -49,6 +52,9 @@ def pgan_variable_shapes(phase, base_shape, latent_dim, kernel_spec, filter_spec
         if i == phase:
             conv(d + f'from_rgb_{phase - 1}', (1, 1, 1), ch, _spec(fs, phase - 2, 1))
     conv(d + 'discriminator_out', _spec(ks, 0, 1), c_in, _spec(fs, 0, 0))
+    from ..ops import minibatch_stddev_settings
+    if minibatch_stddev_settings():      # (not in the reference) the statistic channel's filter, ops.conv3d_minibatch_stddev
+        out[d + MBSTD_WEIGHT] = (*_spec(ks, 0, 1), 1, _spec(fs, 0, 0))
     dense(d + 'discriminator_out/dense_1', v0 * _spec(fs, 0, 0), latent_dim)
     dense(d + 'discriminator_out/dense_2', latent_dim, 1)
     return out

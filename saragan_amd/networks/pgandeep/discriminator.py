@@ -4,7 +4,8 @@ kernel_spec[i-1][1]; convolution j < N takes filter_spec[i-1][N-j-1] filters and
 from_rgb uses filter_spec[.][1]; discriminator_out runs N0 - 1 convolutions with kernel_spec[0][N0-j] and
 filter_spec[0][N0-j-1] before the two dense layers."""
 from ..ops import *  # noqa: F401,F403
-from ..ops import act, apply_bias, conv3d, dense, downscale3d, from_rgb, lerp, materialize, variable_scope
+from ..ops import (act, apply_bias, conv3d, dense, downscale3d, from_rgb, lerp, materialize, minibatch_stddev_settings,
+                   variable_scope)
 from ..specs import filters, kernels
 
 
@@ -51,6 +52,8 @@ def discriminator(x, alpha, phase, latent_dim, activation, kernel_spec, filter_s
     """pgandeep/discriminator.py:97-131."""
     if conditioning is not None:
         raise NotImplementedError()
+    if minibatch_stddev_settings():
+        raise NotImplementedError('minibatch stddev (networks.ops.set_minibatch_stddev) is not offered for the pgandeep networks')
     with variable_scope('discriminator', reuse=is_reuse):
         x_downscale = x
         with variable_scope(f'from_rgb_{phase}'):

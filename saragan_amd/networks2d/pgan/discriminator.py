@@ -35,6 +35,9 @@ def discriminator_out(x, base_dim, latent_dim, filters_out, activation, param):
 
 def discriminator(x, alpha, phase, num_phases, base_dim, latent_dim, activation, param=None, is_reuse=False,
                   size='medium'):
+    from ...networks.ops import minibatch_stddev_settings
+    if minibatch_stddev_settings():
+        raise NotImplementedError('minibatch stddev (networks.ops.set_minibatch_stddev) is not offered for the 2-D networks')
     with variable_scope('discriminator', reuse=is_reuse):
         x = as_volume(x)
         x_downscale = x

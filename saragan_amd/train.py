@@ -59,10 +59,12 @@ def run_training(args, device=None, max_steps_per_phase=None, log_every=1):
     prev_augment = L.set_augment(None)      # (_run_training installs the run's own; the caller's comes back afterwards)
     on = bool(getattr(args, 'd_spectral_norm', False))      # (not in the reference's flags) --d_spectral_norm / --sn_iterations
     prev_spectral = nops.set_spectral_norm(('discriminator/',) if on else (), getattr(args, 'sn_iterations', 1) if on else 1)
+    prev_mbstd = nops.set_minibatch_stddev(getattr(args, 'd_mbstd_group', 0) or 0)      # (not in the reference) --d_mbstd_group
     try:
         return _run_training(args, device, max_steps_per_phase, log_every)
     finally:
         L.set_augment(prev_augment)
+        nops.set_minibatch_stddev(prev_mbstd)
         nops.set_spectral_norm(*prev_spectral)
 
 
@@ -77,6 +79,10 @@ def _run_training(args, device, max_steps_per_phase, log_every):
     torch.cuda.set_device(device)
     set_compute_dtype(torch.bfloat16 if getattr(args, 'dtype', 'bf16') == 'bf16' else torch.float32)
 
+    mbstd_group = nops.minibatch_stddev_settings()
+    if mbstd_group and args.architecture != 'pgan':
+        raise NotImplementedError(f'minibatch stddev (--d_mbstd_group) is offered for the pgan architecture only, got '
+                                  f'{args.architecture!r}')
     discriminator = importlib.import_module(f'saragan_amd.networks.{args.architecture}.discriminator').discriminator
     generator = importlib.import_module(f'saragan_amd.networks.{args.architecture}.generator').generator   # :64-65
 
@@ -120,6 +126,9 @@ def _run_training(args, device, max_steps_per_phase, log_every):
             if batch_size > max_local_batch_size:
                 batch_size = int(max_local_batch_size)
             assert batch_size * global_size <= args.max_global_batch_size
+        if mbstd_group and phase >= args.starting_phase and batch_size % min(mbstd_group, batch_size) != 0:
+            raise ValueError(f'--d_mbstd_group {mbstd_group} does not divide the per-process batch {batch_size} of phase {phase} '
+                             f'(groups are local to a rank)')
         if aug is not None:      # one adjustment moves p by the share of --ada_kimg that `interval` steps show
             aug.delta = batch_size * global_size * aug.interval / ((getattr(args, 'ada_kimg', None) or 500.0) * 1000.0)
         real_image_input = opt.Placeholder(get_current_input_shape(phase, batch_size, args.start_shape))

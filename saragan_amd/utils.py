@@ -101,6 +101,9 @@ def load_checkpoint(path):
     return {k: z[k] for k in z.files}
 
 
+MBSTD_SUFFIX = 'discriminator_out/mbstd/weight'
+
+
 def restore_variables(store, phase, starting_phase, logdir, continue_path, var_list, verbose, ema=None):
     """utils.py:75-118: restore by NAME the variables listed in var_list from model_{phase-1} (or continue_path),
     then set the EMA shadows to the restored values."""
@@ -114,11 +117,26 @@ def restore_variables(store, phase, starting_phase, logdir, continue_path, var_l
     sd = load_checkpoint(restore_path)
     names = [v if isinstance(v, str) else getattr(v, 'key', v.name.replace(':0', '')) for v in var_list]
     missing = [n for n in names if n in store.vars and n not in sd]
+    # (not in the reference) --d_mbstd_group: the statistic channel's filter.  A checkpoint written without the flag has none:
+    # zeros leave the discriminator what the checkpoint's was (the term it scales vanishes), and training moves it from there
+    zeroed = [n for n in missing if n.endswith(MBSTD_SUFFIX)]
+    missing = [n for n in missing if n not in zeroed]
     if missing:
         raise KeyError(f'checkpoint {restore_path} lacks variables {missing}')
+    extra = [k for k in sd if k.endswith(MBSTD_SUFFIX) and k not in store.vars]
+    if extra:
+        raise ValueError(f'checkpoint {restore_path} holds {extra[0]}: it was written with --d_mbstd_group; give the flag '
+                         f'(networks.ops.set_minibatch_stddev) to continue from it')
+    for n in zeroed:
+        if n in store.effective:
+            raise ValueError(f'checkpoint {restore_path} lacks {n}, and a zero filter cannot be spectrally normalised: continue '
+                             f'without --d_spectral_norm, or from a checkpoint written with --d_mbstd_group')
+        with torch.no_grad():
+            store.vars[n].zero_()
+        print(f'Checkpoint {restore_path} has no {n} (written without --d_mbstd_group): starting it from zeros')
     with torch.no_grad():
         for n in names:
-            if n in store.vars:
+            if n in store.vars and n not in zeroed:
                 store.vars[n].copy_(torch.as_tensor(sd[n]).to(store.vars[n].device).reshape(store.vars[n].shape))
                 u = store.u_name(n)      # the state of a normalised weight travels with it; a checkpoint without it: fresh u
                 if n in store.effective and u in sd:
