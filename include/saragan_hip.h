@@ -388,6 +388,18 @@ int sg_mbstd_term_fwd(const void* y, const float* s, const float* B, void* out, 
                       sg_stream_t st);
 int sg_mbstd_term_dot(const void* g, const float* B, float* r, int32_t n, int64_t plane, sg_dtype dt, sg_stream_t st);
 int sg_mbstd_term_outer(const float* s, const void* g, float* Bg, int32_t n, int64_t plane, sg_dtype dt, sg_stream_t st);
+/* Label conditioning of the 3-D pgan (csrc/cond.hip).  c f32 [n, l]: one label row per sample; W f32 [l, zdim]:
+ * the generator's embedding; z [n, zdim], out [n, 2 * zdim], o [n, l] of type dt, row-major.  One launch per call, f32 sums in
+ * ascending index order, no atomics.  SG_EINVAL before any launch: a NULL pointer (but see adjoint), a size < 1.
+ *   sg_cond_embed, adjoint 0:  out[i, :zdim] = z[i],  out[i, zdim + j] = sum_k c[i, k] * W[k, j]
+ *                  adjoint 1:  out holds the gradient g of the forward's output (read); W[k, j] = sum_i c[i, k] * g[i, zdim + j]
+ *                              (f32, i ascending) and z[i, j] = g[i, j] are WRITTEN; W or z may be NULL (not both): not computed.
+ *   sg_cond_project, adjoint 0: out[i] = sum_k o[i, k] * c[i, k]          (out [n] of type dt)
+ *                    adjoint 1: o holds the gradient g [n] of the forward's output; out[i, k] = g[i] * c[i, k]  (out [n, l]).
+ * Each op is linear in z, W / o: the adjoint is its gradient, and the forward is the adjoint's. */
+int sg_cond_embed(void* z, const float* c, float* W, void* out, int32_t n, int32_t zdim, int32_t l, int32_t adjoint, sg_dtype dt,
+                  sg_stream_t st);
+int sg_cond_project(const void* o, const float* c, void* out, int32_t n, int32_t l, int32_t adjoint, sg_dtype dt, sg_stream_t st);
 /* dtype conversion between f32 and bf16 buffers (dst dtype = dt_dst). */
 int sg_cast(const void* src, sg_dtype dt_src, void* dst, sg_dtype dt_dst, int64_t numel, sg_stream_t st);
 

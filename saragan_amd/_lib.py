@@ -113,6 +113,8 @@ SIGNATURES = {
     'sg_mbstd_term_fwd': (C.c_int, [_p, _p, _p, _p, _i32, _i64, C.c_int, _p]),
     'sg_mbstd_term_dot': (C.c_int, [_p, _p, _p, _i32, _i64, C.c_int, _p]),
     'sg_mbstd_term_outer': (C.c_int, [_p, _p, _p, _i32, _i64, C.c_int, _p]),
+    'sg_cond_embed': (C.c_int, [_p, _p, _p, _p, _i32, _i32, _i32, _i32, C.c_int, _p]),
+    'sg_cond_project': (C.c_int, [_p, _p, _p, _i32, _i32, _i32, C.c_int, _p]),
     'sg_cast': (C.c_int, [_p, C.c_int, _p, C.c_int, _i64, _p]),
     'sg_adam_ema': (C.c_int, [_p, _p, _p, _p, _p, _i64, _f, _f, _f, _f, _f, _f, _p]),
     'sg_optim_step': (C.c_int, [C.c_int, _p, _p, _p, _p, _p, _i64, _f, _f, _f, C.c_int, _f, _f, _p]),

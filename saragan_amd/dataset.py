@@ -99,6 +99,8 @@ class NumpyPathDataset:
             self.scratch_dir = os.path.normpath(npy_dir)
             self.scratch_files = list(self.npy_files)
         self._deck = _Deck(len(self.scratch_files), self._rng)
+        self.labels = None             # optional float32 [F, L] table, row i belongs to file i of the sorted table (set_labels)
+        self.last_labels = None        # the label rows of the most recent batch_paths / batch_mpi_paths draw, in its order
         self.shape = self.dtype = None
         if self.scratch_files:
             probe = np.load(self.scratch_files[0], mmap_mode='r')
@@ -141,6 +143,8 @@ class NumpyPathDataset:
         part = object.__new__(NumpyPathDataset)
         part.__dict__.update(self.__dict__)
         part.npy_files, part.scratch_files = self.npy_files[lo:hi], self.scratch_files[lo:hi]
+        part.labels = None if self.labels is None else self.labels[lo:hi]
+        part.last_labels = None
         # children shuffle independently of the parent -- and WITHOUT advancing its generator: the order of the training
         # batches (drawn from the full set: quirk Q3) must not depend on whether a validation split was made
         probe = random.Random()
@@ -176,15 +180,42 @@ class NumpyPathDataset:
         for path in self.samplebuffer:
             print(path)
 
+    # ---- labels (not in the reference's dataset: conditional training, --conditioning_path) ------------------------------
+    def set_labels(self, table):
+        """Attaches a [F, L] table of label rows, row i for file i of the SORTED file table.  Returns self."""
+        table = np.ascontiguousarray(table, dtype=np.float32)
+        if table.ndim != 2 or table.shape[1] < 1:
+            raise ValueError(f'the label table must be a float [F, L] array, got shape {table.shape}')
+        if table.shape[0] != len(self.scratch_files):
+            raise ValueError(f'the label table has {table.shape[0]} rows but the dataset {self.scratch_dir} holds '
+                             f'{len(self.scratch_files)} files')
+        self.labels = table
+        return self
+
+    @property
+    def label_dim(self):
+        return 0 if self.labels is None else int(self.labels.shape[1])
+
+    def labels_of(self, paths):
+        """The label rows [len(paths), L] of the given files of this dataset (None without a table)."""
+        if self.labels is None:
+            return None
+        pos = {p: i for i, p in enumerate(self.scratch_files)}
+        return self.labels[[pos[p] for p in paths]] if len(paths) else self.labels[:0]
+
+    def _drawn(self, positions):
+        self.last_labels = None if self.labels is None else self.labels[positions]
+        return [self.scratch_files[i] for i in positions]
+
     def batch_paths(self, batch_size, auto_repeat=True):
-        return [self.scratch_files[i] for i in self._deck.draw(batch_size, auto_repeat)]
+        return self._drawn(self._deck.draw(batch_size, auto_repeat))
 
     def batch_mpi_paths(self, batch_size, auto_repeat=True):
         """This rank's share of the next global batch: entries rank, rank + world, ... of the drawn positions (column
         `rank` of the reference's reshape(-1, world) before its scatter; a short last draw gives the low ranks one
         more sample, which is what padding with None and stripping it per rank did, dataset.py:316-338)."""
         drawn = self._deck.draw(batch_size * self.world_size, auto_repeat)
-        return [self.scratch_files[i] for i in drawn[self.rank::self.world_size]]
+        return self._drawn(drawn[self.rank::self.world_size])
 
     # ---- materialising ------------------------------------------------------------------------------------
     def load_into(self, paths, out):
@@ -219,7 +250,7 @@ class NumpyPathDataset:
 
 
 class _Slot:
-    __slots__ = ('host', 'dev', 'ready', 'released')
+    __slots__ = ('host', 'dev', 'ready', 'released', 'lab_host', 'lab_dev')
 
 
 class PinnedPrefetcher:
@@ -243,6 +274,7 @@ class PinnedPrefetcher:
         self.free = queue.Queue()
         self.full = queue.Queue(maxsize=depth)
         self.held = None                              # slot index the consumer is reading
+        self.labels = None                            # label rows of the batch next() returned last (device, [N, L])
         self.error = None
         self._stop = threading.Event()
         for i in range(self.nslots):
@@ -258,6 +290,11 @@ class PinnedPrefetcher:
         s.dev = torch.empty(shape, dtype=torch.float32, device=self.device) if self.cuda else s.host
         s.ready = torch.cuda.Event() if self.cuda else None
         s.released = None
+        s.lab_host = s.lab_dev = None
+        if self.ds.labels is not None:      # the batch's label rows travel in the same slot, behind the same events
+            lshape = (shape[0], self.ds.labels.shape[1])
+            s.lab_host = torch.empty(lshape, dtype=torch.float32, pin_memory=self.cuda)
+            s.lab_dev = torch.empty(lshape, dtype=torch.float32, device=self.device) if self.cuda else s.lab_host
         return s
 
     def _work(self):
@@ -271,6 +308,7 @@ class PinnedPrefetcher:
                 except queue.Empty:
                     continue
                 paths = self.ds.batch_mpi_paths(self.bs) if self.dist else self.ds.batch_paths(self.bs)
+                rows = self.ds.last_labels      # (this thread is the only one that draws from the dataset)
                 shape = (len(paths),) + tuple(self.ds.shape)
                 slot = self.slots[i]
                 if slot is None or tuple(slot.host.shape) != shape:
@@ -283,9 +321,13 @@ class PinnedPrefetcher:
                 if self.normalise:
                     np.subtract(host, self.mean, out=host)
                     np.divide(host, self.std, out=host)
+                if rows is not None:
+                    np.copyto(slot.lab_host.numpy(), rows)
                 if self.cuda:
                     with torch.cuda.stream(self.stream):
                         slot.dev.copy_(slot.host, non_blocking=True)
+                        if rows is not None:
+                            slot.lab_dev.copy_(slot.lab_host, non_blocking=True)
                         slot.ready.record(self.stream)
                 while not self._stop.is_set():
                     try:
@@ -321,6 +363,7 @@ class PinnedPrefetcher:
         if self.cuda:
             self.torch.cuda.current_stream(self.device).wait_event(slot.ready)
         self.held = i
+        self.labels = slot.lab_dev      # the label rows of the batch just returned (None without a table); valid as long as it is
         return slot.dev
 
     def close(self):

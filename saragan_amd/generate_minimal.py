@@ -44,7 +44,27 @@ def build_parser():
     p.add_argument('--data_mean', default=None, type=float)
     p.add_argument('--data_stddev', default=None, type=float)
     p.add_argument('--dtype', default='bf16', choices=['bf16', 'f32'], help='activation / MFMA input type (new flag)')
+    p.add_argument('--conditioning', type=str, default=None,
+                   help='(new flag) "v1,...,vL": the label row every sample is generated with; for checkpoints of conditional runs')
+    p.add_argument('--conditioning_path', type=str, default=None,
+                   help='(new flag) a float [num_samples, L] .npy: one label row per sample, in output order')
     return p
+
+
+def label_rows(args):
+    """The [num_samples, L] float32 label table of --conditioning / --conditioning_path, or None."""
+    text, path = getattr(args, 'conditioning', None), getattr(args, 'conditioning_path', None)
+    if text and path:
+        raise ValueError('give --conditioning or --conditioning_path, not both')
+    if text:
+        row = np.array([float(v) for v in text.split(',')], dtype=np.float32)
+        return np.tile(row, (args.num_samples, 1))
+    if path:
+        table = np.asarray(np.load(path), dtype=np.float32)
+        if table.ndim != 2 or table.shape[0] != args.num_samples:
+            raise ValueError(f'--conditioning_path {path}: expected [num_samples = {args.num_samples}, L], got {table.shape}')
+        return table
+    return None
 
 
 def main(args, device='cuda'):
@@ -68,16 +88,29 @@ def main(args, device='cuda'):
     shape = get_current_input_shape(args.phase, args.batch_size, args.start_shape)
     base_shape = get_base_shape(args.start_shape)
     alpha = 0.0                                  # generate_minimal.py:24-25: tf.Variable(0, name='alpha')
+    labels = label_rows(args)
+    made = [0]                                   # samples generated after the restore: sample i reads label row i
 
-    def sample():
+    def sample(count=True):
         z = torch.randn(shape[0], args.latent_dim, device=device, generator=rng)
+        kw = {}
+        if labels is not None:                   # (a last batch that overshoots num_samples repeats the last row)
+            take = np.minimum(np.arange(shape[0]) + made[0], len(labels) - 1)
+            kw['conditioning'] = torch.from_numpy(labels[take]).to(device)
+            made[0] += shape[0] if count else 0
         with use_store(store), torch.no_grad():
             return generator(z, alpha, args.phase, base_shape, activation=args.activation, kernel_spec=args.kernel_spec,
-                             filter_spec=args.filter_spec, param=args.leakiness, size=args.network_size, is_reuse=False)
+                             filter_spec=args.filter_spec, param=args.leakiness, size=args.network_size, is_reuse=False, **kw)
 
-    first = sample()                             # creates the generator's variables (tf.global_variables_initializer)
+    first = sample(count=False)                  # creates the generator's variables (tf.global_variables_initializer)
     print("Restoring variables...")
     sd = load_checkpoint(args.model_path)
+    conditional = 'generator/conditioning/weight' in sd
+    if conditional and labels is None:
+        raise ValueError(f'checkpoint {args.model_path} was written with --conditioning_path: give --conditioning "v1,...,vL" or '
+                         f'--conditioning_path')
+    if labels is not None and not conditional:
+        raise ValueError(f'checkpoint {args.model_path} was written without --conditioning_path: it takes no --conditioning')
     missing = store.load_state_dict({k: v for k, v in sd.items() if k.startswith('generator/')})
     if missing:
         raise KeyError(f'checkpoint {args.model_path} lacks generator variables {missing}')

@@ -118,6 +118,11 @@ def build_parser():
                         'front of the discriminator\'s last convolution, over groups of this many samples (0 = off; pgan only). '
                         'Groups are local to a rank: they are formed inside each process\'s own batch, which the group size must '
                         'divide in every phase, and never span ranks.  DESIGN.md section 4.3')
+    p.add_argument('--conditioning_path', type=none_or_str, default=None,
+                   help='(the reference\'s pgan refuses conditioning) conditional training: a float [F, L] .npy of label rows, '
+                        'one-hot or continuous, row i for file i of every phase directory\'s sorted file table (F = the file '
+                        'count of each of them).  Keep the file outside the phase directories, whose *.npy glob would read it as '
+                        'a volume.  pgan only; a checkpoint written with the flag continues only with it.  DESIGN.md section 4.4')
     p.add_argument('--ema_beta', type=float, default=0.99)
     p.add_argument('--noise_stddev', type=float, required=True)
     p.add_argument('--optimizer', type=none_or_str, choices=[None, 'Adam', 'SGD', 'Momentum', 'Adadelta', 'LAMB', 'AdamW'], default='Adam')
@@ -240,6 +245,8 @@ def finalize_args(args):
             raise SystemExit('--max_consecutive_nonfinite must be >= 1')
     finalize_augment_args(args)
     finalize_mbstd_args(args)
+    if getattr(args, 'conditioning_path', None) and args.architecture != 'pgan':
+        raise SystemExit(f'--conditioning_path is offered for the pgan architecture only, got {args.architecture!r}')
     if getattr(args, 'sn_iterations', 1) != 1 and not getattr(args, 'd_spectral_norm', False):
         raise SystemExit('--sn_iterations needs --d_spectral_norm')
     if getattr(args, 'sn_iterations', 1) < 1:

@@ -35,9 +35,11 @@ def _gather_to_rank0(fake, global_size):
 
 def save_metrics(writer, sess, npy_data, gen_sample, batch_size, global_size, global_step, imagesize_xy, horovod,
                  hyperparam_opt_inter_trial, compute_metrics, num_metric_samples, data_mean, data_stddev, verbose, suffix='',
-                 keep=None):
+                 keep=None, conditioning=None):
     """Same arguments and return value as the reference (a dict with the keys swd, ssim, psnr, mse, nrmse of the enabled
-    metrics).  `keep`: a list that receives (real_batch, fake_batch) of every evaluated batch (tests)."""
+    metrics).  `keep`: a list that receives (real_batch, fake_batch) of every evaluated batch (tests).  `conditioning` (not in
+    the reference): the step graph's label placeholder -- the fakes are generated with the label rows of the real batch they
+    are compared with (npy_data carries the table), sample i with row i, wrapping where the generator's batch overshoots."""
     def log(s):
         if verbose:
             print(s)
@@ -62,17 +64,29 @@ def save_metrics(writer, sess, npy_data, gen_sample, batch_size, global_size, gl
         real_batch = normalize_numpy(real_batch, data_mean, data_stddev, verbose)
         log('Generating fake images for metric computation...')
         start = time.time()
-        fake = sess.run(gen_sample).float()
+        rows, made = None, [0]
+        if conditioning is not None:
+            rows = npy_data.last_labels
+            if rows is None or len(rows) == 0:
+                raise ValueError('conditional metrics need a dataset with a label table (NumpyPathDataset.set_labels)')
+
+        def generate():
+            if rows is None:
+                return sess.run(gen_sample).float()
+            take = (np.arange(conditioning.shape[0]) + made[0]) % len(rows)
+            made[0] += conditioning.shape[0]
+            return sess.run(gen_sample, feed_dict={conditioning: rows[take]}).float()
+        fake = generate()
         if horovod and not hyperparam_opt_inter_trial:
             while fake.shape[0] * global_size < batch_size:
-                fake = torch.cat((fake, sess.run(gen_sample).float()))
+                fake = torch.cat((fake, generate()))
             log(f'Each rank generated {fake.shape[0]} images')
             fake = _gather_to_rank0(fake.contiguous(), global_size)
             if rank0:
                 log(f'Gathered a total of {fake.shape[0]} images')
         else:
             while fake.shape[0] < batch_size:
-                fake = torch.cat((fake, sess.run(gen_sample).float()))
+                fake = torch.cat((fake, generate()))
                 log(f'Generated {fake.shape[0]} images')
         if rank0:
             fake = fake[0:batch_size, ...]

@@ -269,12 +269,13 @@ def _img(x):
 
 
 def forward_generator(generator, discriminator, real_image_input, latent_dim, alpha, phase, base_shape,
-                      kernel_spec, filter_spec, activation, leakiness, loss_fn, noise_stddev, is_reuse=False):
-    """networks/loss.py:4-39."""
+                      kernel_spec, filter_spec, activation, leakiness, loss_fn, noise_stddev, is_reuse=False, conditioning=None):
+    """networks/loss.py:4-39.  conditioning: the label rows [N, L] of the real batch, for G and D alike."""
     rng = _rng(real_image_input.device)
+    cond = _cond(conditioning)
     z = rng.latent(real_image_input.shape[0], latent_dim, real_image_input.device)
     gen_sample = generator(z, alpha, phase, base_shape, activation=activation, kernel_spec=kernel_spec,
-                           filter_spec=filter_spec, param=leakiness, is_reuse=is_reuse)
+                           filter_spec=filter_spec, param=leakiness, is_reuse=is_reuse, **cond)
     real_image_input = rng.add_noise(_img(real_image_input), noise_stddev, 'noise_real')  # drawn as in the reference
     gen_sample_noisy = rng.add_noise(gen_sample, noise_stddev, 'noise_fake')
     # (not in the reference) discriminator augmentation: after the instance noise, before every use by D
@@ -282,7 +283,7 @@ def forward_generator(generator, discriminator, real_image_input, latent_dim, al
     gen_sample_noisy = _augment(rng, gen_sample_noisy, 'aug_fake')
     disc_fake_g = discriminator(gen_sample_noisy, alpha, phase, latent_dim=latent_dim, activation=activation,
                                 kernel_spec=kernel_spec, filter_spec=filter_spec, param=leakiness,
-                                is_reuse=is_reuse).float()
+                                is_reuse=is_reuse, **cond).float()
     if loss_fn == 'wgan':
         gen_loss = -torch.mean(disc_fake_g)
     elif loss_fn == 'logistic':
@@ -292,13 +293,19 @@ def forward_generator(generator, discriminator, real_image_input, latent_dim, al
     return gen_sample, gen_loss
 
 
+def _cond(conditioning):
+    """The keyword a conditional pass adds to a network call (an unconditional one passes none: any callable with the reference's
+    positional signature serves)."""
+    return {} if conditioning is None else dict(conditioning=conditioning)
+
+
 def _gradient_slopes_sq(discriminator, interpolates, alpha, phase, latent_dim, activation, kernel_spec, filter_spec,
-                        leakiness, keep_w):
+                        leakiness, keep_w, conditioning=None):
     """d D(x)/dx at the interpolates with a differentiable graph (tf.gradients at loss.py:74-77 / :136-139),
     then sum of squares over (c,d,h) [keep_w, quirk Q1] or over (c,d,h,w)."""
     interpolates = interpolates.detach().requires_grad_(True)
     d_int = discriminator(interpolates, alpha, phase, latent_dim=latent_dim, is_reuse=True, activation=activation,
-                          kernel_spec=kernel_spec, filter_spec=filter_spec, param=leakiness)
+                          kernel_spec=kernel_spec, filter_spec=filter_spec, param=leakiness, **_cond(conditioning))
     with F.skip_param_grads(current_store().grad_leaves('discriminator/')):   # only d/dx is asked for
         (gradients,) = torch.autograd.grad(d_int, interpolates, grad_outputs=torch.ones_like(d_int),
                                            create_graph=True)
@@ -308,27 +315,28 @@ def _gradient_slopes_sq(discriminator, interpolates, alpha, phase, latent_dim, a
 
 def forward_discriminator(generator, discriminator, real_image_input, latent_dim, alpha, phase, base_shape,
                           kernel_spec, filter_spec, activation, leakiness, loss_fn, gp_weight, noise_stddev,
-                          is_reuse=False):
-    """networks/loss.py:42-98 (gradient penalty over axes (1,2,3,4), loss.py:79)."""
+                          is_reuse=False, conditioning=None):
+    """networks/loss.py:42-98 (gradient penalty over axes (1,2,3,4), loss.py:79).  conditioning: as forward_generator's."""
     rng = _rng(real_image_input.device)
+    cond = _cond(conditioning)
     z = rng.latent(real_image_input.shape[0], latent_dim, real_image_input.device)
     with torch.no_grad():   # every use of gen_sample in this function sits behind tf.stop_gradient
         gen_sample = generator(z, alpha, phase, base_shape, activation=activation, kernel_spec=kernel_spec,
-                               filter_spec=filter_spec, param=leakiness, is_reuse=is_reuse)
+                               filter_spec=filter_spec, param=leakiness, is_reuse=is_reuse, **cond)
     real_image_input = rng.add_noise(_img(real_image_input), noise_stddev, 'noise_real')
     gen_sample_noisy = rng.add_noise(gen_sample, noise_stddev, 'noise_fake')
     # (not in the reference) discriminator augmentation: after the instance noise, before every use by D
     real_image_input = _augment(rng, real_image_input, 'aug_real')
     gen_sample_noisy = _augment(rng, gen_sample_noisy, 'aug_fake')
     net = dict(latent_dim=latent_dim, activation=activation, kernel_spec=kernel_spec, filter_spec=filter_spec,
-               param=leakiness)
+               param=leakiness, **cond)
     disc_fake_d = discriminator(gen_sample_noisy.detach(), alpha, phase, **net).float()
     disc_real = discriminator(real_image_input, alpha, phase, is_reuse=True, **net).float()
     _AUGMENT['cfg'].update(disc_real)
     gamma = rng.gamma(real_image_input.shape[0], real_image_input.device)
     interpolates = F.interpolate_rows(gamma, real_image_input, gen_sample_noisy)      # f32 weights, one rounding
     slopes = torch.sqrt(_gradient_slopes_sq(discriminator, interpolates, alpha, phase, latent_dim, activation,
-                                            kernel_spec, filter_spec, leakiness, keep_w=False))
+                                            kernel_spec, filter_spec, leakiness, keep_w=False, conditioning=conditioning))
     if loss_fn == 'wgan':
         gradient_penalty = (slopes - 1) ** 2
         gp_loss = gp_weight * gradient_penalty
@@ -348,7 +356,9 @@ def forward_discriminator(generator, discriminator, real_image_input, latent_dim
 def forward_simultaneous(generator, discriminator, real_image_input, latent_dim, alpha, phase, base_shape,
                          kernel_spec, filter_spec, activation, leakiness, loss_fn, gp_weight, noise_stddev,
                          conditioning=None):
-    """networks/loss.py:101-165, including quirk Q1 (slopes keeps the W axis: loss.py:140)."""
+    """networks/loss.py:101-165, including quirk Q1 (slopes keeps the W axis: loss.py:140).  conditioning: the label rows [N, L] of
+    the real batch -- the generated batch is made with them, and all three discriminator passes (real, generated, interpolates)
+    read the same rows (the batched real+generated pass: repeated)."""
     rng = _rng(real_image_input.device)
     z = rng.latent(real_image_input.shape[0], latent_dim, real_image_input.device)
     gen_sample = generator(z, alpha, phase, base_shape, activation=activation, kernel_spec=kernel_spec,
@@ -371,8 +381,9 @@ def forward_simultaneous(generator, discriminator, real_image_input, latent_dim,
         # backward, twice the tiles for the low-resolution layers.
         fake_in = gen_sample_noisy.detach().requires_grad_(True)
         n_real = real_image_input.shape[0]
+        both_net = net if conditioning is None else dict(net, conditioning=torch.cat([conditioning, conditioning], dim=0))
         with mbstd_segments(2):
-            both = discriminator(torch.cat([real_image_input, fake_in], dim=0), alpha, phase, **net).float()
+            both = discriminator(torch.cat([real_image_input, fake_in], dim=0), alpha, phase, **both_net).float()
         disc_real, disc_fake_g = both[:n_real], both[n_real:]
         disc_fake_d = disc_fake_g
     else:
@@ -386,7 +397,7 @@ def forward_simultaneous(generator, discriminator, real_image_input, latent_dim,
     # quirk Q1 belongs to the 3-D tree's 5-D tensors; the 2-D tree reduces its 4-D gradient over every non-batch axis
     keep_w = not getattr(discriminator, 'sg_gp_full_reduction', False)
     slopes = torch.sqrt(_gradient_slopes_sq(discriminator, interpolates, alpha, phase, latent_dim, activation,
-                                            kernel_spec, filter_spec, leakiness, keep_w=keep_w))
+                                            kernel_spec, filter_spec, leakiness, keep_w=keep_w, conditioning=conditioning))
     if loss_fn == 'wgan':
         gradient_penalty = (slopes - 1) ** 2
         if not keep_w:

@@ -267,16 +267,51 @@ def apply_bias(x, lrmul=1):
     return F.bias_act(_val(x), b, False, 0.0)
 
 
-def dense(x, fmaps, activation, lrmul=1, param=None):
-    """networks/ops.py:139-144 (flatten is C-major of NCDHW, as tf.reshape on the reference's tensors)."""
+def dense(x, fmaps, activation, lrmul=1, param=None, logits=False):
+    """networks/ops.py:139-144 (flatten is C-major of NCDHW, as tf.reshape on the reference's tensors).  logits (not in the
+    reference): this is the discriminator's logit layer whatever its width (label projection: one unit per label)."""
     x = _val(x)
     if len(x.shape) > 2:
         x = x.reshape(x.shape[0], int(np.prod(x.shape[1:])))
     w = get_weight([x.shape[1], fmaps], activation, lrmul=lrmul, param=param)
     # the discriminator's logit layer (one output unit) runs in f32 whatever the compute dtype: the losses add terms
     # 1000x apart (wgan drift 1e-3 * D(real)^2 next to D(fake) - D(real), loss.py:146-151), below bf16 resolution
-    dt = torch.float32 if fmaps == 1 else compute_dtype()
+    dt = torch.float32 if (fmaps == 1 or logits) else compute_dtype()
     return _LazyConv(x.to(dt), w.var, w.coef, False)
+
+
+# ---- label conditioning (not in the reference's pgan; its surfgan tree: networks/surfgan/g_mapping.py:20-25,
+# networks/surfgan/discriminator.py:68-69; DESIGN.md 4.4) ---------------------------------------------------------------------
+def label_rows(conditioning, architecture='pgan'):
+    """None, or the labels of a conditional pass: a floating [N, L] tensor, one row per sample.  Anything else is refused the way
+    the reference's pgan refuses every conditioning."""
+    if conditioning is None:
+        return None
+    if architecture != 'pgan':
+        raise NotImplementedError(f'conditioning is offered for the 3-D pgan architecture only, not for {architecture}')
+    if not (torch.is_tensor(conditioning) and conditioning.dim() == 2 and conditioning.is_floating_point()):
+        raise NotImplementedError('pgan conditioning takes a floating [N, L] tensor of label rows, got '
+                                  f'{type(conditioning).__name__}'
+                                  + (f' {conditioning.dtype} {tuple(conditioning.shape)}' if torch.is_tensor(conditioning) else ''))
+    return conditioning
+
+
+def label_embedding(z, conditioning):
+    """concat([z, c @ weight], axis=1) with the variable `conditioning/weight` [L, latent_dim] of the current scope: N(0,1), a
+    plain matmul without the equalised-LR coefficient (g_mapping.py:23-24).  One launch (functional.cond_embed)."""
+    if conditioning.shape[0] != z.shape[0]:
+        raise ValueError(f'conditioning holds {conditioning.shape[0]} label rows for {z.shape[0]} latents')
+    with variable_scope('conditioning'):
+        w = get_variable('weight', [conditioning.shape[1], z.shape[1]], 'normal')
+    return F.cond_embed(z.to(compute_dtype()), conditioning, w)
+
+
+def label_projection(x, conditioning):
+    """sum_l x[n, l] * c[n, l] as [N, 1] (surfgan/discriminator.py:69).  One launch (functional.cond_project)."""
+    x = _val(x)
+    if conditioning.shape[0] != x.shape[0]:
+        raise ValueError(f'conditioning holds {conditioning.shape[0]} label rows for a batch of {x.shape[0]}')
+    return F.cond_project(x, conditioning)
 
 
 def conv3d(x, fmaps, kernel, activation, param=None, lrmul=1):

@@ -2,8 +2,8 @@
 error behaviour); the ops are saragan_amd.networks.ops (gfx950 kernels)."""
 from ..ops import *  # noqa: F401,F403
 from ..specs import filters, kernels
-from ..ops import (act, apply_bias, conv3d, conv3d_minibatch_stddev, dense, downscale3d, from_rgb, lerp, materialize,
-                   minibatch_stddev_settings, variable_scope)
+from ..ops import (act, apply_bias, conv3d, conv3d_minibatch_stddev, dense, downscale3d, from_rgb, label_projection, label_rows,
+                   lerp, materialize, minibatch_stddev_settings, variable_scope)
 
 
 def discriminator_block(x, activation, kernel_spec, filter_spec, i, param=None):
@@ -22,8 +22,9 @@ def discriminator_block(x, activation, kernel_spec, filter_spec, i, param=None):
     return x
 
 
-def discriminator_out(x, latent_dim, activation, kernel_spec, filter_spec, param):
-    """pgan/discriminator.py:48-68.  minibatch_stddev_layer (:50, commented out in the reference) stays disabled unless
+def discriminator_out(x, latent_dim, activation, kernel_spec, filter_spec, param, conditioning=None):
+    """pgan/discriminator.py:48-68.  conditioning (label rows [N, L]): dense_2 has L outputs and the logit is their label-weighted
+    sum (networks/surfgan/discriminator.py:68-69 of the reference).  minibatch_stddev_layer (:50, commented out in the reference) stays disabled unless
     ops.set_minibatch_stddev turned it on: then the first convolution is the reference's layer on concat(x, statistic),
     evaluated without the concatenation (ops.conv3d_minibatch_stddev)."""
     with variable_scope('discriminator_out'):
@@ -39,16 +40,19 @@ def discriminator_out(x, latent_dim, activation, kernel_spec, filter_spec, param
             x = apply_bias(x)
             x = act(x, activation, param=param)
         with variable_scope('dense_2'):
-            x = dense(x, 1, activation='linear')
-            x = apply_bias(x)
+            if conditioning is None:
+                x = dense(x, 1, activation='linear')
+                x = apply_bias(x)
+            else:
+                x = dense(x, conditioning.shape[1], activation='linear', logits=True)
+                x = label_projection(apply_bias(x), conditioning)
         return x
 
 
 def discriminator(x, alpha, phase, latent_dim, activation, kernel_spec, filter_spec, param=None, is_reuse=False,
                   conditioning=None):
-    """pgan/discriminator.py:71-108."""
-    if conditioning is not None:
-        raise NotImplementedError()
+    """pgan/discriminator.py:71-108.  conditioning (refused by the reference's pgan): a floating [N, L] tensor of label rows."""
+    conditioning = label_rows(conditioning)
     with variable_scope('discriminator', reuse=is_reuse):
         x_downscale = x
         with variable_scope(f'from_rgb_{phase}'):
@@ -62,5 +66,5 @@ def discriminator(x, alpha, phase, latent_dim, activation, kernel_spec, filter_s
                                             filters(filter_spec, phase - 2, 1), activation,
                                             param=param)
                 x = lerp(fromrgb_prev, x, alpha)       # alpha * fromrgb_prev + (1 - alpha) * x
-        x = discriminator_out(x, latent_dim, activation, kernel_spec, filter_spec, param)
+        x = discriminator_out(x, latent_dim, activation, kernel_spec, filter_spec, param, conditioning)
         return materialize(x)

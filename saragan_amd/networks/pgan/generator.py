@@ -4,8 +4,8 @@ import numpy as np
 
 from ..ops import *  # noqa: F401,F403  (the reference does `from networks.ops import *`)
 from ..specs import filters, kernels
-from ..ops import (act, apply_bias, conv3d, dense, lerp, materialize, pixel_norm, to_rgb, upscale3d,
-                   variable_scope)
+from ..ops import (act, apply_bias, conv3d, dense, label_embedding, label_rows, lerp, materialize, pixel_norm, to_rgb,
+                   upscale3d, variable_scope)
 
 
 def generator_in(x, shape, activation, kernel_spec, filter_spec, param=None):
@@ -45,10 +45,12 @@ def generator_block(x, activation, kernel_spec, filter_spec, i, param=None):
 
 def generator(x, alpha, phase, base_shape, activation, kernel_spec, filter_spec, param=None, size='medium',
               is_reuse=False, conditioning=None):
-    """pgan/generator.py:74-103."""
-    if conditioning is not None:
-        raise NotImplementedError()
+    """pgan/generator.py:74-103.  conditioning (refused by the reference's pgan): a floating [N, L] tensor of label rows; their
+    learned embedding is concatenated to the latents, as the reference's surfgan mapping network does."""
+    conditioning = label_rows(conditioning)
     with variable_scope('generator', reuse=is_reuse):
+        if conditioning is not None:
+            x = label_embedding(x, conditioning)
         with variable_scope('generator_in'):
             x = generator_in(x, shape=base_shape[1:], activation=activation, kernel_spec=kernel_spec,
                              filter_spec=filter_spec, param=param)

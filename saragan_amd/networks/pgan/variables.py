@@ -16,7 +16,16 @@ def _spec(spec, phase_i, layer_i):
     return spec[phase_i][layer_i]
 
 
-def pgan_variable_shapes(phase, base_shape, latent_dim, kernel_spec, filter_spec):
+CONDITIONING_WEIGHT = 'generator/conditioning/weight'      # exists only in a conditional graph (label_dim > 0)
+
+
+def pgan_variable_shapes(phase, base_shape, latent_dim, kernel_spec, filter_spec, label_dim=0):
+    """label_dim (not in the reference's pgan): the width L of the label rows of a conditional graph -- the generator gains the
+    embedding [L, latent_dim] and its first dense layer reads 2 * latent_dim inputs, the discriminator's dense_2 has L outputs.
+    0: the reference's plan."""
+    label_dim = int(label_dim)
+    if label_dim < 0:
+        raise ValueError('label_dim >= 0 (0: unconditional)')
     ch = base_shape[0]
     v0 = int(np.prod(base_shape[1:]))
     fs, ks = filter_spec, kernel_spec
@@ -31,7 +40,9 @@ def pgan_variable_shapes(phase, base_shape, latent_dim, kernel_spec, filter_spec
         out[scope + '/bias'] = (cout,)
 
     g = 'generator/'
-    dense(g + 'generator_in/dense', latent_dim, v0 * _spec(fs, 0, 0))
+    if label_dim:
+        out[CONDITIONING_WEIGHT] = (label_dim, latent_dim)
+    dense(g + 'generator_in/dense', (2 if label_dim else 1) * latent_dim, v0 * _spec(fs, 0, 0))
     conv(g + 'generator_in/conv', _spec(ks, 0, 1), _spec(fs, 0, 0), _spec(fs, 0, 1))
     c_prev = _spec(fs, 0, 1)
     for i in range(2, phase + 1):
@@ -56,7 +67,7 @@ def pgan_variable_shapes(phase, base_shape, latent_dim, kernel_spec, filter_spec
     if minibatch_stddev_settings():      # (not in the reference) the statistic channel's filter, ops.conv3d_minibatch_stddev
         out[d + MBSTD_WEIGHT] = (*_spec(ks, 0, 1), 1, _spec(fs, 0, 0))
     dense(d + 'discriminator_out/dense_1', v0 * _spec(fs, 0, 0), latent_dim)
-    dense(d + 'discriminator_out/dense_2', latent_dim, 1)
+    dense(d + 'discriminator_out/dense_2', latent_dim, label_dim or 1)
     return out
 
 

@@ -51,7 +51,7 @@ def discriminator(x, alpha, phase, latent_dim, activation, kernel_spec, filter_s
                   conditioning=None):
     """pgandeep/discriminator.py:97-131."""
     if conditioning is not None:
-        raise NotImplementedError()
+        raise NotImplementedError('conditioning is offered for the 3-D pgan architecture only, not for pgandeep')
     if minibatch_stddev_settings():
         raise NotImplementedError('minibatch stddev (networks.ops.set_minibatch_stddev) is not offered for the pgandeep networks')
     with variable_scope('discriminator', reuse=is_reuse):

@@ -44,7 +44,7 @@ def generator(x, alpha, phase, base_shape, activation, kernel_spec, filter_spec,
               is_reuse=False, conditioning=None):
     """pgandeep/generator.py:97-122."""
     if conditioning is not None:
-        raise NotImplementedError()
+        raise NotImplementedError('conditioning is offered for the 3-D pgan architecture only, not for pgandeep')
     if phase > len(kernel_spec):
         kernels(kernel_spec, phase - 1, 0)      # raises the reference's ValueError for a missing phase
     with variable_scope('generator', reuse=is_reuse):

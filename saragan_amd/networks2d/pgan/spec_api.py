@@ -11,7 +11,7 @@ from . import generator as _g
 def generator(x, alpha, phase, base_shape, activation, kernel_spec, filter_spec, param=None, size='medium', is_reuse=False,
               conditioning=None):
     if conditioning is not None:
-        raise NotImplementedError()
+        raise NotImplementedError('conditioning is offered for the 3-D pgan architecture only, not for the 2-D networks')
     fs = filter_spec
     img = _g.generator(x, alpha, phase, fs['num_phases'], fs['base_dim'], [base_shape[0], *base_shape[-2:]], activation,
                        param=param, size=fs['size'], is_reuse=is_reuse)
@@ -21,7 +21,7 @@ def generator(x, alpha, phase, base_shape, activation, kernel_spec, filter_spec,
 def discriminator(x, alpha, phase, latent_dim, activation, kernel_spec, filter_spec, param=None, is_reuse=False,
                   conditioning=None):
     if conditioning is not None:
-        raise NotImplementedError()
+        raise NotImplementedError('conditioning is offered for the 3-D pgan architecture only, not for the 2-D networks')
     fs = filter_spec
     return _d.discriminator(x, alpha, phase, fs['num_phases'], fs['base_dim'], latent_dim, activation, param=param,
                             is_reuse=is_reuse, size=fs['size'])

@@ -372,6 +372,7 @@ class StepGraph:
         self.flat_ready = False
         self.allreduce = None  # parallel.GradientAllReducer
         self.world = 1
+        self._cond = None      # the label rows of the step in flight (a conditional graph; run() sets them)
         on, max_consecutive = nonfinite_guard_settings()
         self.guard = NonFiniteGuard(max_consecutive) if on else None
 
@@ -485,7 +486,25 @@ class StepGraph:
         return runs
 
     # -- execution ----------------------------------------------------------------------------------
-    def run(self, fetches, feed):
+    def _labels(self, cond, n):
+        """The label rows of a step or a gen_sample fetch: None for an unconditional graph, else the fed [n, L] rows (f32, on
+        the device)."""
+        ph = self.cfg.get('conditioning')
+        if ph is None:
+            if cond is not None:
+                raise ValueError('conditioning was fed to a step graph built without it (optimize_step(..., conditioning=...))')
+            return None
+        if cond is None:
+            raise ValueError('conditioning must be fed')
+        if tuple(cond.shape) != (int(n), int(ph.shape[1])):
+            raise ValueError(f'conditioning: expected label rows of shape {(int(n), int(ph.shape[1]))}, got {tuple(cond.shape)}')
+        return cond
+
+    def _cond_kw(self):
+        """conditioning=... for the loss builders of a conditional graph (none otherwise: their calls are what they were)."""
+        return {} if self._cond is None else dict(conditioning=self._cond)
+
+    def run(self, fetches, feed, cond=None):
         c = self.cfg
         self._ensure_flat()
         train_ids = sorted({f.net for f in fetches if f.key in ('train', 'gradients', 'max_norm')})
@@ -499,12 +518,15 @@ class StepGraph:
             from .networks import loss as L
             n = c['placeholder'].shape[0]
             dev = self.store.device if real is None else real.device
+            cond = self._labels(cond, n)
+            kw = {} if cond is None else dict(conditioning=cond.to(dev))
             with use_store(self.store), torch.no_grad():
                 alpha = float(c['alpha'].eval()) if isinstance(c['alpha'], ScalarVariable) else float(c['alpha'])
                 z = L._rng(dev).latent(n, c['latent_dim'], dev)
                 sample = c['generator'](z, alpha, c['phase'], c['base_shape'], activation=c['activation'],
-                                        kernel_spec=c['kernel_spec'], filter_spec=c['filter_spec'], param=c['leakiness'])
+                                        kernel_spec=c['kernel_spec'], filter_spec=c['filter_spec'], param=c['leakiness'], **kw)
             return [sample.detach() for _ in fetches]
+        self._cond = self._labels(cond, real.shape[0])
         self._stepped = True
         self._refuse_spectral_with_adasum()
         if self.guard is not None:
@@ -554,13 +576,13 @@ class StepGraph:
         g_ids = [t for t in train_ids if self.trains[t]['net'] == 'generator']
         self._refresh_effective(force=True)
         disc_loss, gp_loss = forward_discriminator(c['generator'], c['discriminator'], real, *net_args,
-                                                   c['gp_weight'], c['noise_stddev'])
+                                                   c['gp_weight'], c['noise_stddev'], **self._cond_kw())
         out.update(disc_loss=disc_loss, gp_loss=gp_loss)
         for tid in d_ids:
             self._finish(tid, self._backward(tid, out), out, apply=tid in want_train, lr_dev=lr_dev.get(tid), marks=marks)
         self._refresh_effective(force=True)      # (the updated discriminator)
         gen_sample, gen_loss = forward_generator(c['generator'], c['discriminator'], real, *net_args,
-                                                 c['noise_stddev'], is_reuse=True)
+                                                 c['noise_stddev'], is_reuse=True, **self._cond_kw())
         out.update(gen_sample=gen_sample, gen_loss=gen_loss)
         for tid in g_ids:
             self._finish(tid, self._backward(tid, out), out, apply=tid in want_train, lr_dev=lr_dev.get(tid), marks=marks)
@@ -574,10 +596,10 @@ class StepGraph:
         if nets >= {'generator', 'discriminator'}:
             with linear_generator_link():   # wgan: G's gradient through D comes out of D's own backward
                 gen_loss, disc_loss, gp_loss, gen_sample = forward_simultaneous(
-                    c['generator'], c['discriminator'], real, *net_args, c['gp_weight'], c['noise_stddev'])
+                    c['generator'], c['discriminator'], real, *net_args, c['gp_weight'], c['noise_stddev'], **self._cond_kw())
         else:
             gen_loss, disc_loss, gp_loss, gen_sample = forward_simultaneous(
-                c['generator'], c['discriminator'], real, *net_args, c['gp_weight'], c['noise_stddev'])
+                c['generator'], c['discriminator'], real, *net_args, c['gp_weight'], c['noise_stddev'], **self._cond_kw())
         out.update(gen_loss=gen_loss, disc_loss=disc_loss, gp_loss=gp_loss, gen_sample=gen_sample)
         if hasattr(gen_loss, 'sg_link'):    # the discriminator's backward must run first: it feeds G's
             train_ids = sorted(train_ids, key=lambda t: self.trains[t]['net'] != 'discriminator')
@@ -595,8 +617,8 @@ class StepGraph:
     # ONCE into a hipGraph (torch.cuda.graph: the C-ABI launches go to torch's current stream, which is the capturing one;
     # workspaces come from the graphs' shared private pool) and replayed as a single launch.  What varies per step is on
     # the device or outside the captured region:
-    #   * the batch, the latents and the penalty's mixing weights live in fixed buffers refilled before each replay
-    #     (loss.StaticRandom), the instance noise reads its Philox offset from a device counter;
+    #   * the batch, the label rows of a conditional graph, the latents and the penalty's mixing weights live in fixed buffers
+    #     refilled before each replay (loss.StaticRandom), the instance noise reads its Philox offset from a device counter;
     #   * the fade-in weights [alpha, 1 - alpha] (networks/ops.py:4-23: alpha moves EVERY step of a mixing phase) and each
     #     optimiser's step size (lr schedule optimization.py:227-296; Adam's bias correction) are host arithmetic written to
     #     a pinned mirror and sent with one small copy before the replay (functional.DevScalars; sg_axpby_dev,
@@ -604,7 +626,7 @@ class StepGraph:
     #   * with a gradient reducer attached (parallel.DistributedOptimizer) the captured region ends after the backward
     #     passes; the bucket collectives and the optimiser launches follow eagerly (RCCL stays outside the graph).
     # The graph is keyed by what is baked in (train ops, whether gradient norms are asked for, alpha's class {0, 1, in
-    # between}, batch shape, dtype) -- NOT by the loss / sample fetches: every capture produces all of them -- and captured
+    # between}, batch shape, the label width L, dtype) -- NOT by the loss / sample fetches: every capture produces all of them -- and captured
     # after three eager steps of the same key (every lazy one-time call has happened).
     # SARAGAN_HIPGRAPH=1 forces capture, =0 forbids it; unset, a key is captured when its eager steps turn out host-bound
     # (host enqueue time >= 0.8 x the device span of the step, measured on eager steps 2 and 3 of the key).
@@ -649,7 +671,8 @@ class StepGraph:
         dist_ids = tuple(t for t in train_ids if self.trains[t]['optimizer'].distributed is not None)
         key = (tuple(train_ids), tuple(sorted(want_train)), norms, alpha_class, tuple(real.shape), str(compute_dtype()), strategy,
                self.guard is not None,
-               strategy == 'simultaneous' and 'discriminator/' in self.store.rewritten)      # (a pending refresh is baked in)
+               strategy == 'simultaneous' and 'discriminator/' in self.store.rewritten,      # (a pending refresh is baked in)
+               None if self._cond is None else int(self._cond.shape[1]))
         caps = self.__dict__.setdefault('_captures', {})
         ent = caps.get(key)
         if ent is None:
@@ -705,6 +728,9 @@ class StepGraph:
                 old = min((k for k, e in caps.items() if 'graph' in e), key=lambda k: caps[k]['used'])
                 del caps[old]
             ent['real'] = real.clone()
+            fed_cond = self._cond
+            ent['cond'] = None if fed_cond is None else fed_cond.clone()      # the captured launches read the labels from here
+            self._cond = ent['cond']
             ent['rnd'] = L.StaticRandom(base, real.shape[0], self.cfg['latent_dim'], real.device,
                                         pattern=('z', 'g', 'z') if strategy == 'alternate' else ('z', 'g'))
             ent['rnd'].draw()
@@ -790,13 +816,14 @@ class StepGraph:
                 for _, o, _ in ent['opt']:
                     o.t -= 1
                 ent['decided'] = 'eager'
-                for k_ in ('real', 'rnd', 'scalars', 'opt', 'glr', 'out', 'pend'):
+                for k_ in ('real', 'cond', 'rnd', 'scalars', 'opt', 'glr', 'out', 'pend'):
                     ent.pop(k_, None)
                 # a kept filter-gradient workspace first made inside the failed capture had its zero-fill only RECORDED: it
                 # (and any other) goes, the next eager step makes clean ones
                 F.clear_kept_workspaces()
                 raise
             finally:
+                self._cond = fed_cond
                 L.set_random_source(base)
                 F.mark_packs_stale()      # (a capture records launches without running them)
             ent['rnd'].counting = False
@@ -810,6 +837,8 @@ class StepGraph:
             ent['graph'] = g
         else:
             ent['real'].copy_(real, non_blocking=True)
+            if ent['cond'] is not None:
+                ent['cond'].copy_(self._cond, non_blocking=True)
             ent['rnd'].draw()
             ent['rnd'].sync_counter()
             sc = ent['scalars']
@@ -980,8 +1009,10 @@ class StepGraph:
 
 def optimize_step(optimizer_gen, optimizer_disc, generator, discriminator, real_image_input, latent_dim, alpha, phase,
                   base_shape, kernel_spec, filter_spec, activation, leakiness, loss_fn, gp_weight, optim_strategy,
-                  g_clipping, d_clipping, noise_stddev, freeze_vars=None):
-    """optimization.py:77-224: returns the same 20-tuple (handles for Session.run)."""
+                  g_clipping, d_clipping, noise_stddev, freeze_vars=None, conditioning=None):
+    """optimization.py:77-224: returns the same 20-tuple (handles for Session.run).  conditioning (the reference keeps
+    `# conditioning=real_label` at :182): a second Placeholder([N, L]) for the label rows of the real batch; Session.run reads
+    them from feed_dict for every step and every gen_sample fetch of the graph (3-D pgan only)."""
     if optim_strategy not in ('simultaneous', 'alternate'):
         raise ValueError("Unknown optim strategy ", optim_strategy)
     if loss_fn not in ('wgan', 'logistic'):
@@ -998,7 +1029,17 @@ def optimize_step(optimizer_gen, optimizer_disc, generator, discriminator, real_
         plan = importlib.import_module(arch_pkg + '.variables').variable_shapes
     except (ImportError, AttributeError, ValueError):
         plan = pgan_variable_shapes
-    shapes = plan(phase, base_shape, latent_dim, kernel_spec, filter_spec)
+    if conditioning is not None:
+        if not isinstance(conditioning, Placeholder) or len(conditioning.shape) != 2 or int(conditioning.shape[1]) < 1:
+            raise ValueError('optimize_step: conditioning is a Placeholder([N, L]) with L >= 1')
+        if int(conditioning.shape[0]) != int(real_image_input.shape[0]):
+            raise ValueError(f'optimize_step: conditioning holds {conditioning.shape[0]} rows for a batch of '
+                             f'{real_image_input.shape[0]}')
+        if plan is not pgan_variable_shapes:
+            raise NotImplementedError(f'conditioning is offered for the 3-D pgan architecture only, not for {arch_pkg}')
+        shapes = plan(phase, base_shape, latent_dim, kernel_spec, filter_spec, label_dim=int(conditioning.shape[1]))
+    else:
+        shapes = plan(phase, base_shape, latent_dim, kernel_spec, filter_spec)
     for name, shp in shapes.items():           # create in the reference's order (weights N(0,1), biases 0)
         store.get(name, shp, 'normal' if name.endswith('weight') else 'zeros')
     from .networks import ops as nops
@@ -1009,7 +1050,7 @@ def optimize_step(optimizer_gen, optimizer_disc, generator, discriminator, real_
     cfg = dict(sn_iterations=nops.spectral_norm_settings()[1], generator=generator, discriminator=discriminator, latent_dim=latent_dim, alpha=alpha, phase=phase,
                base_shape=base_shape, kernel_spec=kernel_spec, filter_spec=filter_spec, activation=activation,
                leakiness=leakiness, loss_fn=loss_fn, gp_weight=gp_weight, optim_strategy=optim_strategy,
-               noise_stddev=noise_stddev, freeze_names=freeze_names, placeholder=real_image_input)
+               noise_stddev=noise_stddev, freeze_names=freeze_names, placeholder=real_image_input, conditioning=conditioning)
     graph = StepGraph(store, cfg)
     gen_loss, disc_loss = Fetch(graph, 'gen_loss'), Fetch(graph, 'disc_loss')
     gp_loss, gen_sample = Fetch(graph, 'gp_loss'), Fetch(graph, 'gen_sample')
@@ -1089,8 +1130,15 @@ class Session:
                 raise TypeError(f'cannot run {f!r}')
         for graph, idxs in graphs.values():
             ph = graph.cfg['placeholder']
+            cond = None
+            cph = graph.cfg.get('conditioning')
+            if cph is not None and feed_dict is not None and cph in feed_dict:
+                cond = feed_dict[cph]
+                if not torch.is_tensor(cond):
+                    cond = torch.from_numpy(np.ascontiguousarray(cond))
+                cond = cond.to(self.device, torch.float32, non_blocking=True).contiguous()
             if all(fl[i].key == 'gen_sample' for i in idxs) and (feed_dict is None or ph not in feed_dict):
-                vals = graph.run([fl[i] for i in idxs], None)      # the generator alone needs no real batch
+                vals = graph.run([fl[i] for i in idxs], None, cond)      # the generator alone needs no real batch
                 for i, v in zip(idxs, vals):
                     results[i] = v
                 continue
@@ -1100,7 +1148,7 @@ class Session:
             if not torch.is_tensor(batch):
                 batch = torch.from_numpy(np.ascontiguousarray(batch))
             batch = batch.to(self.device, torch.float32, non_blocking=True)
-            vals = graph.run([fl[i] for i in idxs], batch)
+            vals = graph.run([fl[i] for i in idxs], batch, cond)
             for i, v in zip(idxs, vals):
                 results[i] = v
         return results[0] if single else results

@@ -37,6 +37,21 @@ def get_numpy_dataset(phase, starting_phase, start_shape, dataset_path, scratch_
                             is_correct_phase=phase >= starting_phase, rank=rank, world_size=world, seed=seed)
 
 
+def load_label_table(path, dataset_path=None, start_shape=None, num_phases=0):
+    """--conditioning_path (not in the reference): a float [F, L] .npy, row i for file i of every phase directory's SORTED file
+    table.  The file may not lie in a phase directory: that directory's `*.npy` glob would take it for a volume."""
+    table = np.load(path)
+    if table.ndim != 2 or table.shape[1] < 1 or not (np.issubdtype(table.dtype, np.floating) or np.issubdtype(table.dtype, np.integer)):
+        raise ValueError(f'--conditioning_path {path}: expected a numeric [F, L] array, got {table.dtype} {table.shape}')
+    here = os.path.dirname(os.path.abspath(path))
+    for phase in range(1, num_phases + 1):
+        size = get_xy_dim(phase, start_shape)
+        if os.path.abspath(os.path.join(dataset_path, f'{size}x{size}')) == here:
+            raise ValueError(f'--conditioning_path {path} lies in the phase directory {here}: its *.npy files are the volumes; '
+                             f'keep the label table outside the phase directories')
+    return np.ascontiguousarray(table, dtype=np.float32)
+
+
 def augment_config(args, device):
     """The --augment* / --ada_* flags (main.py; not in the reference) -> loss.AugmentConfig, or None with --augment none.  One
     object for the whole run: the probability and the controller's sums persist across phases."""
@@ -100,6 +115,12 @@ def _run_training(args, device, max_steps_per_phase, log_every):
     stats = {}
     aug = augment_config(args, device)
     L.set_augment(aug)
+    label_table = None      # (not in the reference) --conditioning_path: conditional training, DESIGN.md 4.4
+    if getattr(args, 'conditioning_path', None):
+        if args.architecture != 'pgan':
+            raise NotImplementedError(f'conditioning (--conditioning_path) is offered for the pgan architecture only, got '
+                                      f'{args.architecture!r}')
+        label_table = load_label_table(args.conditioning_path, args.dataset_path, args.start_shape, num_phases)
 
     for phase in range(1, ending_phase + 1):
         np.random.seed(seed); random.seed(seed); torch.manual_seed(seed)   # :102-109
@@ -107,6 +128,8 @@ def _run_training(args, device, max_steps_per_phase, log_every):
         npy_data = get_numpy_dataset(phase, args.starting_phase, args.start_shape, args.dataset_path,
                                      args.scratch_path, verbose, rank if horovod else 0, global_size, seed=args.seed,
                                      local_rank=local)
+        if label_table is not None:      # (F must be the file count of this phase's directory: set_labels names both)
+            npy_data.set_labels(label_table)
         # :121-124: the split keeps the file order (consecutive scans of one patient stay on one side); quirk Q3: the
         # training batches below are still drawn from the FULL set npy_data, as the reference's are (:423-425)
         vf, tf_ = getattr(args, 'validation_fraction', 0.0) or 0.0, getattr(args, 'test_fraction', 0.0) or 0.0
@@ -132,6 +155,7 @@ def _run_training(args, device, max_steps_per_phase, log_every):
         if aug is not None:      # one adjustment moves p by the share of --ada_kimg that `interval` steps show
             aug.delta = batch_size * global_size * aug.interval / ((getattr(args, 'ada_kimg', None) or 500.0) * 1000.0)
         real_image_input = opt.Placeholder(get_current_input_shape(phase, batch_size, args.start_shape))
+        conditioning = None if label_table is None else opt.Placeholder([batch_size, label_table.shape[1]], name='conditioning')
         num_metric_samples = get_num_metric_samples(getattr(args, 'num_metric_samples', None), batch_size, global_size)  # :144
         calc_metrics = bool(getattr(args, 'calc_metrics', False)) and npy_data_validation is not None
         metric_flags = get_compute_metrics_dict(args)
@@ -141,7 +165,7 @@ def _run_training(args, device, max_steps_per_phase, log_every):
             kept = [] if metric_tap is not None else None
             m = save_metrics(None, sess, subset, gen_sample, getattr(args, 'metrics_batch_size', 16), global_size, global_step,
                              get_xy_dim(phase, args.start_shape), horovod, False, metric_flags, nsamples, args.data_mean,
-                             args.data_stddev, verbose, suffix=suffix, keep=kept)
+                             args.data_stddev, verbose, suffix=suffix, keep=kept, conditioning=conditioning)
             if metric_tap is not None:
                 metric_tap.append((phase, tag + suffix, m, kept))
             return m
@@ -171,7 +195,8 @@ def _run_training(args, device, max_steps_per_phase, log_every):
             tup = opt.optimize_step(optimizer_gen, optimizer_disc, generator, discriminator, real_image_input,
                                     args.latent_dim, alpha, phase, base_shape, args.kernel_spec, args.filter_spec,
                                     args.activation, args.leakiness, args.loss_fn, args.gp_weight, args.optim_strategy,
-                                    args.g_clipping, args.d_clipping, args.noise_stddev, prev_vars)
+                                    args.g_clipping, args.d_clipping, args.noise_stddev, prev_vars,
+                                    **({} if conditioning is None else dict(conditioning=conditioning)))
         (train_gen, train_disc, gen_loss, disc_loss, gp_loss, gen_sample, _gg, g_variables, _dg, d_variables, _mg, _md,
          train_gen_freeze, _ggf, _gvf, _mgf, train_disc_freeze, _dgf, _dvf, _mdf) = tup
         graph = tup[0].graph
@@ -223,11 +248,13 @@ def _run_training(args, device, max_steps_per_phase, log_every):
             else:
                 train_g, train_d = train_gen, train_disc
             want_log = verbose and (local_step // batch_size) % log_every == 0
+            feed = {real_image_input: batch}
+            if conditioning is not None:
+                feed[conditioning] = loader.labels      # the rows of this batch's files, staged next to it
             if want_log:
-                _, _, d_loss_t, g_loss_t = sess.run([train_g, train_d, disc_loss, gen_loss],
-                                                    feed_dict={real_image_input: batch})
+                _, _, d_loss_t, g_loss_t = sess.run([train_g, train_d, disc_loss, gen_loss], feed_dict=feed)
             else:
-                sess.run([train_g, train_d], feed_dict={real_image_input: batch})
+                sess.run([train_g, train_d], feed_dict=feed)
             sess.run(ema_op)
             if local_step == batch_size:
                 # The phase's graph, variables and closures live until the phase ends: taken out of the cyclic collector's

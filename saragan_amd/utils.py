@@ -102,6 +102,7 @@ def load_checkpoint(path):
 
 
 MBSTD_SUFFIX = 'discriminator_out/mbstd/weight'
+CONDITIONING_WEIGHT = 'generator/conditioning/weight'      # (networks/pgan/variables.py) present exactly in conditional graphs
 
 
 def restore_variables(store, phase, starting_phase, logdir, continue_path, var_list, verbose, ema=None):
@@ -116,6 +117,18 @@ def restore_variables(store, phase, starting_phase, logdir, continue_path, var_l
         print("Restoring variables from:", restore_path)
     sd = load_checkpoint(restore_path)
     names = [v if isinstance(v, str) else getattr(v, 'key', v.name.replace(':0', '')) for v in var_list]
+    # (not in the reference) --conditioning_path: a conditional network's first dense layer and logit layer have other shapes,
+    # so neither kind of checkpoint can start the other kind of run
+    if CONDITIONING_WEIGHT in store.vars and CONDITIONING_WEIGHT not in sd:
+        raise ValueError(f'checkpoint {restore_path} lacks {CONDITIONING_WEIGHT}: it was written without --conditioning_path and '
+                         f'cannot start a conditional run; continue without --conditioning_path, or from a checkpoint written '
+                         f'with it')
+    if CONDITIONING_WEIGHT in sd and CONDITIONING_WEIGHT not in store.vars:
+        raise ValueError(f'checkpoint {restore_path} holds {CONDITIONING_WEIGHT}: it was written with --conditioning_path; give '
+                         f'the flag (optimize_step(..., conditioning=...)) to continue from it')
+    if CONDITIONING_WEIGHT in sd and tuple(sd[CONDITIONING_WEIGHT].shape) != tuple(store.vars[CONDITIONING_WEIGHT].shape):
+        raise ValueError(f'checkpoint {restore_path} was written with --conditioning_path rows of width '
+                         f'{sd[CONDITIONING_WEIGHT].shape[0]}, this run\'s have {store.vars[CONDITIONING_WEIGHT].shape[0]}')
     missing = [n for n in names if n in store.vars and n not in sd]
     # (not in the reference) --d_mbstd_group: the statistic channel's filter.  A checkpoint written without the flag has none:
     # zeros leave the discriminator what the checkpoint's was (the term it scales vanishes), and training moves it from there
