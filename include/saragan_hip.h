@@ -634,6 +634,25 @@ int sg_ssim_mean(const double* ux, const double* uy, const double* uxx, const do
                  int32_t s0, int32_t s1, int32_t s2, int32_t c, int32_t crop0, int32_t crop, double cov_norm, double c1,
                  double c2, void* workspace, size_t workspace_bytes, sg_stream_t st);
 
+/* ---- squared distances between every pair of volumes (metrics/sample_metrics.py: MMD, 1-NN accuracy, precision/recall) ----
+ * a [ma, v] and b [mb, v]: f32, row-major, contiguous, on the device; out: f64 [ma, mb],
+ *   out[i][j] = max(0, |a_i|^2 + |b_j|^2 - 2 a_i.b_j).
+ * The dot products are f32-input MFMAs (exact f32 products, f32 fmaf chain) over at most sg_pairwise_sqdist_chunk()
+ * consecutive voxels; each chunk's accumulators are added into f64.  The row norms are summed in f64 throughout and the
+ * combination is f64.  The grid comes from splitting v: partial tiles go to the workspace and are added in ascending
+ * split order -- no floating-point atomics, two calls on the same input give the same bits whatever SG_DETERMINISTIC says.
+ * b == a (same pointer, mb == ma) is the symmetric case: only tiles on and above the diagonal are computed, out[j][i] is
+ * out[i][j] bit for bit and the diagonal is exactly 0.  Every offset is 64-bit (ma * v may exceed 2^32); ma, mb need not
+ * be multiples of the tile nor v of the K step or the chunk, and nothing is padded or copied.
+ * workspace: sg_pairwise_sqdist_workspace(ma, mb, v) bytes (covers the symmetric call of the same sizes), 8-byte aligned.
+ * SG_EINVAL before any launch: a NULL pointer, ma < 1, mb < 1, v < 1.  SG_EWORKSPACE: the workspace is too small.
+ * SG_EALIGN: a, b not 4-byte or out, workspace not 8-byte aligned.  16-byte aligned inputs with v % 4 == 0 are read by
+ * 16-byte loads. */
+int32_t sg_pairwise_sqdist_chunk(void);      /* the longest f32 accumulation chain, in elements of v */
+size_t sg_pairwise_sqdist_workspace(int32_t ma, int32_t mb, int64_t v);
+int sg_pairwise_sqdist(const float* a, const float* b, double* out, int32_t ma, int32_t mb, int64_t v, void* workspace,
+                       size_t workspace_bytes, sg_stream_t st);
+
 /* ---- opt-in kernel timing (used by bench.py's roofline leg) ------------------------------------- */
 /* When enabled, every sg_conv3d_fwd / sg_conv3d_wgrad launch is bracketed by hipEvents on its stream.
  * sg_prof_collect synchronises those events and returns, per kind (0 = conv fwd, 1 = wgrad) and per

@@ -153,6 +153,9 @@ SIGNATURES = {
     'sg_minmax': (C.c_int, [_p, _p, _i64, _p, _sz, _p]),
     'sg_ssim_products': (C.c_int, [_p, _p, _p, _p, _p, _i64, _p]),
     'sg_ssim_mean': (C.c_int, [_p, _p, _p, _p, _p, _p, _i32, _i32, _i32, _i32, _i32, _i32, C.c_double, C.c_double, C.c_double, _p, _sz, _p]),
+    'sg_pairwise_sqdist_chunk': (_i32, []),
+    'sg_pairwise_sqdist_workspace': (_sz, [_i32, _i32, _i64]),
+    'sg_pairwise_sqdist': (C.c_int, [_p, _p, _p, _i32, _i32, _i64, _p, _sz, _p]),
     'sg_prof_enable': (C.c_int, [C.c_int]),
     'sg_prof_enabled': (C.c_int, []),
     'sg_prof_collect': (C.c_int, [C.POINTER(ProfEntry), _i32, C.POINTER(_i32)]),

@@ -158,6 +158,13 @@ def build_parser():
     p.add_argument('--metrics_batch_size', default=16, type=int)
     for m in ('FID', 'swds', 'ssims', 'psnrs', 'mses', 'nrmses'):
         p.add_argument(f'--compute_{m}', default=False, action='store_true')
+    # (new flags) download-free set statistics over the pooled evaluated samples: metrics/sample_metrics.py
+    p.add_argument('--compute_mmd', default=False, action='store_true', help='unbiased Gaussian-kernel MMD^2 of reals and fakes')
+    p.add_argument('--compute_nn_accuracy', default=False, action='store_true',
+                   help='leave-one-out 1-NN two-sample accuracy (0.5 is ideal)')
+    p.add_argument('--compute_precision_recall', default=False, action='store_true',
+                   help='k-NN precision (fidelity) and recall (coverage: low under mode collapse)')
+    p.add_argument('--pr_k', default=3, type=int, help='neighbour rank of the precision / recall radii')
     p.add_argument('--dtype', default='bf16', choices=['bf16', 'f32'], help='activation / MFMA input type (new flag)')
     p.add_argument('--max_steps_per_phase', type=int, default=None, help='smoke runs: cap the steps per phase (new flag)')
     return p

@@ -6,21 +6,27 @@ metrics/swd.py and metrics/skim_metrics.py), average over the batches and print 
 What differs, and why: there is no tf.summary writer (TensorBoard is out of scope: `writer` is accepted and ignored);
 MPI.COMM_WORLD.Gather of the ranks' fake images (save_metrics.py:117-131) is torch.distributed.gather to rank 0; FID needs
 the Inception graph the reference downloads (metrics/fid_new.py:291-318): --compute_FID is answered with a printed notice at
-every evaluation and no 'FID' key."""
+every evaluation and no 'FID' key.  In its place (not in the reference): --compute_mmd, --compute_nn_accuracy and
+--compute_precision_recall, three download-free two-sample statistics over the POOLED evaluated batches
+(metrics/sample_metrics.py)."""
 import time
 
 import numpy as np
 import torch
 
+from .. import _lib
 from ..dataset import normalize_numpy
+from . import sample_metrics as SM
 from . import skim_metrics as SK
 from . import swd as SWD
+
+SAMPLE_FLAGS = ('compute_mmd', 'compute_nn_accuracy', 'compute_precision_recall')
 
 
 def get_compute_metrics_dict(args):
     """utils.py:267-277."""
     return {k: bool(getattr(args, k, False)) for k in
-            ('compute_FID', 'compute_swds', 'compute_ssims', 'compute_psnrs', 'compute_mses', 'compute_nrmses')}
+            ('compute_FID', 'compute_swds', 'compute_ssims', 'compute_psnrs', 'compute_mses', 'compute_nrmses') + SAMPLE_FLAGS}
 
 
 def _gather_to_rank0(fake, global_size):
@@ -35,11 +41,15 @@ def _gather_to_rank0(fake, global_size):
 
 def save_metrics(writer, sess, npy_data, gen_sample, batch_size, global_size, global_step, imagesize_xy, horovod,
                  hyperparam_opt_inter_trial, compute_metrics, num_metric_samples, data_mean, data_stddev, verbose, suffix='',
-                 keep=None, conditioning=None):
+                 keep=None, conditioning=None, pr_k=3, keep_sets=None):
     """Same arguments and return value as the reference (a dict with the keys swd, ssim, psnr, mse, nrmse of the enabled
     metrics).  `keep`: a list that receives (real_batch, fake_batch) of every evaluated batch (tests).  `conditioning` (not in
     the reference): the step graph's label placeholder -- the fakes are generated with the label rows of the real batch they
-    are compared with (npy_data carries the table), sample i with row i, wrapping where the generator's batch overshoots."""
+    are compared with (npy_data carries the table), sample i with row i, wrapping where the generator's batch overshoots.
+    compute_mmd / compute_nn_accuracy / compute_precision_recall (not in the reference; metrics/sample_metrics.py) are set
+    statistics: the evaluated batches stay on the device and are evaluated once, pooled, after the loop (keys mmd,
+    nn_accuracy[_real|_fake], precision, recall).  `pr_k`: the neighbour rank of precision / recall.  `keep_sets`: a list
+    that receives (n, distance matrix as numpy) when that evaluation ran (tests)."""
     def log(s):
         if verbose:
             print(s)
@@ -58,6 +68,8 @@ def save_metrics(writer, sess, npy_data, gen_sample, batch_size, global_size, gl
         import torch.distributed as dist
         rank0 = dist.get_rank() == 0
     swds_local, psnrs_local, mses_local, nrmses_local, ssims_local = [], [], [], [], []
+    pool_sets = any(compute_metrics.get(f) for f in SAMPLE_FLAGS)
+    reals_kept, fakes_kept = [], []
     counter = 0
     while True:
         real_batch = npy_data.batch_mpi(batch_size) if horovod else npy_data.batch(batch_size)      # :94-97
@@ -97,6 +109,9 @@ def save_metrics(writer, sess, npy_data, gen_sample, batch_size, global_size, gl
             fake = fake[0:real.shape[0]]
             if keep is not None:
                 keep.append((real.cpu().numpy(), fake.cpu().numpy()))
+            if pool_sets:
+                reals_kept.append(real.reshape(real.shape[0], -1).to(torch.float32))
+                fakes_kept.append(fake.reshape(fake.shape[0], -1).to(torch.float32))
             for flag, fn, dest, name in (('compute_swds', SWD.get_swd_for_volumes, swds_local, 'swds'),
                                          ('compute_psnrs', SK.get_psnr, psnrs_local, 'psnrs'),
                                          ('compute_ssims', SK.get_ssim, ssims_local, 'ssims'),
@@ -125,4 +140,42 @@ def save_metrics(writer, sess, npy_data, gen_sample, batch_size, global_size, gl
         if compute_metrics.get('compute_swds'):
             metrics['swd'] = np.array(swds_local).mean(axis=0)
             log(f"SWDS: {metrics['swd']}")
+        if pool_sets:
+            metrics.update(_sample_set_metrics(reals_kept, fakes_kept, compute_metrics, pr_k, keep_sets, log))
     return metrics
+
+
+def _sample_set_metrics(reals, fakes, compute_metrics, pr_k, keep_sets, log):
+    """MMD^2, 1-NN accuracy and precision / recall of the pooled evaluated batches: ONE distance matrix.  Never raises for
+    a set that is too small or too large: the statistic (or all three) is switched off with a printed notice."""
+    n = sum(r.shape[0] for r in reals)
+    which = []
+    for flag, name, need, what in (('compute_mmd', 'mmd', 2, 'MMD'), ('compute_nn_accuracy', 'nn_accuracy', 1, '1-NN accuracy'),
+                                   ('compute_precision_recall', 'precision_recall', pr_k + 1, f'Precision / recall (k={pr_k})')):
+        if compute_metrics.get(flag):
+            if n >= need and pr_k >= 1:
+                which.append(name)
+            else:
+                print(f'{what} is switched off for this evaluation: {n} samples per set, it needs {need}')
+    if not which:
+        return {}
+    v = reals[0].shape[1]
+    need_bytes = 2 * n * v * 4 + (2 * n) ** 2 * 8 + _lib.load().sg_pairwise_sqdist_workspace(2 * n, 2 * n, v)
+    free_bytes = torch.cuda.mem_get_info(reals[0].device)[0]
+    if need_bytes > free_bytes:
+        print(f'MMD / 1-NN accuracy / precision and recall are skipped for this evaluation: the pooled set of {2 * n} volumes '
+              f'and its distance matrix need {need_bytes} bytes, {free_bytes} are free on the device')
+        return {}
+    t0 = time.time()
+    D = SM.pairwise_sqdist(torch.cat(reals + fakes, dim=0))
+    if keep_sets is not None:
+        keep_sets.append((n, D.cpu().numpy()))
+    try:
+        m = SM.metrics_from_matrix(D, n, pr_k, None, which)
+    except ValueError as e:      # (a degenerate set: all reals identical leaves MMD without a bandwidth)
+        print(f'MMD / 1-NN accuracy / precision and recall are skipped for this evaluation: {e}')
+        return {}
+    print("sample metrics took %s" % (time.time() - t0))
+    for line in SM.format_lines(m, pr_k):
+        log(line)
+    return m
