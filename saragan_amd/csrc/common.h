@@ -46,6 +46,7 @@ struct sg_config {
   int wgrad_no_w16;                          // SG_WGRAD_NO_W16: 16-wide levels back on conv_wgrad2 (diagnostic)
   int wgrad3l_min_cols;                      // SG_WGRAD3L_MIN_COLS: fewest tile columns the sliding-halo weight gradient takes (0: 2)
   int wgrad3l_16;                            // SG_WGRAD3L_16: the sliding-halo weight gradient on v_mfma_f32_16x16x32_bf16
+  int wgrad3l_reuse;                         // SG_WGRAD3L_REUSE (default 1): tap columns per wave, each halo row read once per column; 0: tap = wave + 4 j
   int wgrad_v1_blocks;                       // SG_WGRAD_V1_BLOCKS: block target of the generic weight-gradient kernel (0: default)
   int dbg_flags;                             // SG_DBG_FLAGS
   int no_small;                              // SG_NO_SMALL: the small-channel 2-D layers through the MFMA kernels (A/B, tests)

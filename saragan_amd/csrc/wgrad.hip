@@ -1179,11 +1179,228 @@ struct sg_wgrad_tile_lean16 {
   }
 };
 
-template <bool UPS, bool DYM = false, int TW = 32, bool M16 = false>   // UPS: x is the half-resolution tensor, gathered nearest-x2 (upscale3d fused into
+// The same tile with every halo row read ONCE per tap column (SG_WGRAD3L_REUSE, the default).  The three taps (kh = 0, 1, 2) of a
+// column c = kd * 3 + kw read the same x fragment whenever th + kh is equal: halo row r of the column feeds kh = 0 at tile row
+// r, kh = 1 at r - 1 and kh = 2 at r - 2.  A wave owns whole columns (sg_wg3l_tap), so one read feeds up to three MFMAs, and kh
+// moves into the instruction offset: one base register per (td, column).  What is held across rows is the dy side: tile row th
+// of dy is live while rows th .. th + 2 of x pass, a ring of four fragments (16 VGPRs against the 8 of the loop above, and 6 base
+// registers against 14: the register count stays where it was).
+// A tile is walked as blocks (td, W half); within a block, row by row: [dy row r] [column A row r] [column B row r] [slot 6 row r],
+// the dy and slot-6 items only for r < TH.  Every item is one pair of transposing reads, issued PF items ahead; an x item waits
+// once (lgkmcnt = 2 x the items issued behind it) and then issues its 1-3 MFMAs.  Per tile and wave: NBLK * (3 TH + 4) x reads
+// (64 for 32-wide tiles, 56 for 16-wide ones, against 112) and the same 16 dy reads for the same 112 MFMAs.
+// For 32-wide tiles this permutes the 16 K steps of a tile ((td, half, th) instead of (td, th, half)): a tap's f32 sum may
+// differ from the loop above in the last bit, the latitude two runs in atomic mode have anyway; a given build and shape
+// always sums in the same order, so slab mode (SG_DETERMINISTIC) stays bit-reproducible.
+template <int PF, int TW = 32>
+struct sg_wgrad_tile_reuse {
+  static constexpr int MAXT = 7, TH = 128 / TW, HW = TW + 2, KPL = TW / 16, NBLK = 2 * KPL, ROWS = TH + 2;
+  static constexpr int IPB = 4 * TH + 4, XPB = 3 * TH + 4, NI = NBLK * IPB, RING = PF + 1, YRING = 4;
+  static constexpr int XREADS = NBLK * XPB, YREADS = NBLK * TH, MFMAS = NBLK * TH * MAXT;     // per tile and wave
+  static_assert(XREADS <= (TW == 32 ? 64 : 56) && YREADS == 16 && MFMAS == 112, "read budget of the row-reuse loop");
+  static_assert((ROWS - 1) * HW * 64 + (KPL - 1) * 1024 + 256 < 65536, "kh lives in the 16-bit instruction offset");
+  static_assert(PF * 2 <= 15, "lgkmcnt is a 4-bit counter");
+  // dy row r (item 4 r of its block) is requested at item 4 r - PF and lands in the slot of row r - 4, whose last MFMA
+  // (column B, kh = 2, row r - 2) is item 4 r - 6: the request must be issued behind it
+  static_assert(PF <= 5, "the dy ring of four rows");
+  typedef s16x4 frag_t;
+  struct Ctx {
+    int xb[2][3];      // per td: column A, column B (lane part + ring slot + kw), slot 6 (+ its kh; the bias slot: the image of ones)
+    int yb;            // lane part of the dy image
+  };
+  struct It { int blk, r, kind, xi; };      // kind 0: dy row, 1 / 2: column A / B, 3: slot 6; xi: running index of the x items
+  static constexpr It item(int I) {
+    const int blk = I / IPB, q = I % IPB;
+    if (q < 4 * TH) return It{blk, q / 4, q % 4, blk * XPB + (q / 4) * 3 + (q % 4) - 1};
+    return It{blk, TH + (q - 4 * TH) / 2, 1 + (q - 4 * TH) % 2, blk * XPB + 3 * TH + (q - 4 * TH)};
+  }
+  template <int I>
+  static __device__ __forceinline__ void load(const Ctx& c, frag_t (&a0)[RING], frag_t (&a1)[RING], frag_t (&b0)[YRING],
+                                              frag_t (&b1)[YRING]) {
+    constexpr It it = item(I);
+    constexpr int td = it.blk / KPL, half = it.blk % KPL;
+    if constexpr (it.kind == 0) {
+      constexpr int ks = (td * TH + it.r) * KPL + half;
+      asm volatile("ds_read_b64_tr_b16 %0, %1 offset:%2" : "=v"(b0[it.r % YRING]) : "v"(c.yb), "n"(ks * 1024));
+      asm volatile("ds_read_b64_tr_b16 %0, %1 offset:%2" : "=v"(b1[it.r % YRING]) : "v"(c.yb), "n"(ks * 1024 + 256));
+    } else {
+      constexpr int SL = it.xi % RING, off = it.r * HW * 64 + half * 1024;
+      asm volatile("ds_read_b64_tr_b16 %0, %1 offset:%2" : "=v"(a0[SL]) : "v"(c.xb[td][it.kind - 1]), "n"(off));
+      asm volatile("ds_read_b64_tr_b16 %0, %1 offset:%2" : "=v"(a1[SL]) : "v"(c.xb[td][it.kind - 1]), "n"(off + 256));
+    }
+  }
+  static __device__ __forceinline__ u32x4 cat(const frag_t& lo, const frag_t& hi) {
+    u32x4 o;
+    o[0] = __builtin_bit_cast(u32x2, lo)[0]; o[1] = __builtin_bit_cast(u32x2, lo)[1];
+    o[2] = __builtin_bit_cast(u32x2, hi)[0]; o[3] = __builtin_bit_cast(u32x2, hi)[1];
+    return o;
+  }
+  template <int J, int T>      // slot J takes the x fragment against tile row T of dy
+  static __device__ __forceinline__ void mm(f32x16 (&acc)[MAXT], const u32x4& af, frag_t (&b0)[YRING], frag_t (&b1)[YRING]) {
+    acc[J] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(__builtin_bit_cast(bf16x8, af),
+                                                    __builtin_bit_cast(bf16x8, cat(b0[T % YRING], b1[T % YRING])), acc[J], 0, 0, 0);
+  }
+  template <int I>
+  static __device__ __forceinline__ void step(const Ctx& c, f32x16 (&acc)[MAXT], frag_t (&a0)[RING], frag_t (&a1)[RING],
+                                              frag_t (&b0)[YRING], frag_t (&b1)[YRING]) {
+    if constexpr (I < NI) {
+      if constexpr (I + PF < NI) load<I + PF>(c, a0, a1, b0, b1);
+      constexpr It it = item(I);
+      if constexpr (it.kind != 0) {
+        constexpr int younger = (NI - 1 - I < PF ? NI - 1 - I : PF) * 2;
+        asm volatile("s_waitcnt lgkmcnt(%0)" ::"n"(younger));
+        __builtin_amdgcn_sched_barrier(0);
+        constexpr int SL = it.xi % RING;
+        const u32x4 af = cat(a0[SL], a1[SL]);
+        if constexpr (it.kind == 3) {
+          mm<6, it.r>(acc, af, b0, b1);
+        } else {
+          constexpr int j0 = (it.kind - 1) * 3;
+          if constexpr (it.r < TH) mm<j0, it.r>(acc, af, b0, b1);
+          if constexpr (it.r >= 1 && it.r - 1 < TH) mm<j0 + 1, it.r - 1>(acc, af, b0, b1);
+          if constexpr (it.r >= 2) mm<j0 + 2, it.r - 2>(acc, af, b0, b1);
+        }
+        __builtin_amdgcn_sched_barrier(0);
+      }
+      step<I + 1>(c, acc, a0, a1, b0, b1);
+    }
+  }
+  template <int I>
+  static __device__ __forceinline__ void prologue(const Ctx& c, frag_t (&a0)[RING], frag_t (&a1)[RING], frag_t (&b0)[YRING],
+                                                  frag_t (&b1)[YRING]) {
+    if constexpr (I < PF && I < NI) {
+      load<I>(c, a0, a1, b0, b1);
+      prologue<I + 1>(c, a0, a1, b0, b1);
+    }
+  }
+  static __device__ __forceinline__ void run(const Ctx& c, f32x16 (&acc)[MAXT]) {
+    frag_t a0[RING], a1[RING], b0[YRING], b1[YRING];
+    SG_KLOOP_BEGIN();
+    prologue<0>(c, a0, a1, b0, b1);
+    step<0>(c, acc, a0, a1, b0, b1);
+    SG_KLOOP_END();
+  }
+};
+
+// The row-reuse loop on v_mfma_f32_16x16x32_bf16, 32-wide tiles (a K step is one tile row).  Blocks (td, ci half h); per row:
+// [dy co half 0] [dy co half 1] [column A] [column B] [slot 6]; an x item (16 channels x 32 voxels of one halo row) feeds up to
+// 3 kh x 2 co halves = 6 MFMAs.  Every accumulator tile [h][hb] still sees its K steps in the order (td, th) of
+// sg_wgrad_tile_lean16: the sums have the same bits.  The dy rows are read once per ci-half sweep (32 items against 16),
+// the x items fall from 112 to 64.  (16-wide tiles pair two rows per K step, where only kh = 0 / 2 share fragments: they keep
+// sg_wgrad_tile_lean16 with the column tap table.)
+template <int PF>
+struct sg_wgrad_tile_reuse16 {
+  static constexpr int MAXT = 7, TH = 4, HW = 34, NBLK = 4, ROWS = TH + 2;
+  static constexpr int IPB = 5 * TH + 4, XPB = 3 * TH + 4, NI = NBLK * IPB, RING = PF + 1, YRING = 4;
+  static constexpr int XREADS = NBLK * XPB, YREADS = NBLK * 2 * TH, MFMAS = NBLK * TH * MAXT * 2;
+  static_assert(XREADS <= 64 && YREADS == 32 && MFMAS == 224, "read budget of the row-reuse loop");
+  static_assert((ROWS - 1) * HW * 64 + 32 + 256 < 65536, "kh lives in the 16-bit instruction offset");
+  static_assert(PF * 2 <= 15, "lgkmcnt is a 4-bit counter");
+  // dy row r (items 5 r, 5 r + 1) is requested from item 5 r - PF on into the slot of row r - 4, last used by item 5 r - 7
+  static_assert(PF <= 6, "the dy ring of four rows");
+  typedef s16x4 frag_t;
+  struct Ctx {
+    int xb[2][3];      // per td: column A, column B, slot 6 (the bias slot: the image of ones)
+    int yb;
+  };
+  struct HF { frag_t p[2]; };
+  struct It { int blk, r, kind, xi; };      // kind 0 / 1: dy co half, 2 / 3: column A / B, 4: slot 6
+  static constexpr It item(int I) {
+    const int blk = I / IPB, q = I % IPB;
+    if (q < 5 * TH) return It{blk, q / 5, q % 5, blk * XPB + (q / 5) * 3 + (q % 5) - 2};
+    return It{blk, TH + (q - 5 * TH) / 2, 2 + (q - 5 * TH) % 2, blk * XPB + 3 * TH + (q - 5 * TH)};
+  }
+  template <int I>
+  static __device__ __forceinline__ void load(const Ctx& c, HF (&a)[RING], HF (&b)[YRING][2]) {
+    constexpr It it = item(I);
+    constexpr int td = it.blk / 2, h = it.blk % 2;
+    if constexpr (it.kind < 2) {
+      constexpr int off = (td * TH + it.r) * 2048 + it.kind * 32;
+      asm volatile("ds_read_b64_tr_b16 %0, %1 offset:%2" : "=v"(b[it.r % YRING][it.kind].p[0]) : "v"(c.yb), "n"(off));
+      asm volatile("ds_read_b64_tr_b16 %0, %1 offset:%2" : "=v"(b[it.r % YRING][it.kind].p[1]) : "v"(c.yb), "n"(off + 256));
+    } else {
+      constexpr int SL = it.xi % RING, off = it.r * HW * 64 + h * 32;
+      asm volatile("ds_read_b64_tr_b16 %0, %1 offset:%2" : "=v"(a[SL].p[0]) : "v"(c.xb[td][it.kind - 2]), "n"(off));
+      asm volatile("ds_read_b64_tr_b16 %0, %1 offset:%2" : "=v"(a[SL].p[1]) : "v"(c.xb[td][it.kind - 2]), "n"(off + 256));
+    }
+  }
+  static __device__ __forceinline__ u32x4 cat(const HF& f) {
+    u32x4 o;
+    o[0] = __builtin_bit_cast(u32x2, f.p[0])[0]; o[1] = __builtin_bit_cast(u32x2, f.p[0])[1];
+    o[2] = __builtin_bit_cast(u32x2, f.p[1])[0]; o[3] = __builtin_bit_cast(u32x2, f.p[1])[1];
+    return o;
+  }
+  template <int J, int H, int T>      // slot J, ci half H: the x fragment against both co halves of tile row T of dy
+  static __device__ __forceinline__ void mm(f32x4 (&acc)[MAXT][4], const u32x4& af, HF (&b)[YRING][2]) {
+#pragma unroll
+    for (int hb = 0; hb < 2; ++hb)
+      acc[J][H * 2 + hb] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(__builtin_bit_cast(bf16x8, af), __builtin_bit_cast(bf16x8, cat(b[T % YRING][hb])),
+                                                                   acc[J][H * 2 + hb], 0, 0, 0);
+  }
+  template <int I>
+  static __device__ __forceinline__ void step(const Ctx& c, f32x4 (&acc)[MAXT][4], HF (&a)[RING], HF (&b)[YRING][2]) {
+    if constexpr (I < NI) {
+      if constexpr (I + PF < NI) load<I + PF>(c, a, b);
+      constexpr It it = item(I);
+      if constexpr (it.kind >= 2) {
+        constexpr int younger = (NI - 1 - I < PF ? NI - 1 - I : PF) * 2;
+        asm volatile("s_waitcnt lgkmcnt(%0)" ::"n"(younger));
+        __builtin_amdgcn_sched_barrier(0);
+        constexpr int SL = it.xi % RING, h = it.blk % 2;
+        const u32x4 af = cat(a[SL]);
+        if constexpr (it.kind == 4) {
+          mm<6, h, it.r>(acc, af, b);
+        } else {
+          constexpr int j0 = (it.kind - 2) * 3;
+          if constexpr (it.r < TH) mm<j0, h, it.r>(acc, af, b);
+          if constexpr (it.r >= 1 && it.r - 1 < TH) mm<j0 + 1, h, it.r - 1>(acc, af, b);
+          if constexpr (it.r >= 2) mm<j0 + 2, h, it.r - 2>(acc, af, b);
+        }
+        __builtin_amdgcn_sched_barrier(0);
+      }
+      step<I + 1>(c, acc, a, b);
+    }
+  }
+  template <int I>
+  static __device__ __forceinline__ void prologue(const Ctx& c, HF (&a)[RING], HF (&b)[YRING][2]) {
+    if constexpr (I < PF && I < NI) {
+      load<I>(c, a, b);
+      prologue<I + 1>(c, a, b);
+    }
+  }
+  static __device__ __forceinline__ void run(const Ctx& c, f32x4 (&acc)[MAXT][4]) {
+    HF a[RING], b[YRING][2];
+    SG_KLOOP_BEGIN();
+    prologue<0>(c, a, b);
+    step<0>(c, acc, a, b);
+    SG_KLOOP_END();
+  }
+};
+
+// Tap of slot j of wave w.  RU (row reuse): by columns c = kd * 3 + kw -- wave w owns columns 2 w and 2 w + 1, kh = 0, 1, 2 in
+// slots 0-2 and 3-5; slot 6 of waves 0-2 holds the three taps of column 8 (kh = w), slot 6 of wave 3 is spare (27: the bias
+// slot).  Otherwise tap = w + 4 j, where wave 3's slot 6 is the spare one too.
+__host__ __device__ constexpr int sg_wg3l_tap(bool ru, int w, int j) {
+  if (!ru) return w + 4 * j;
+  if (j < 6) return ((2 * w + j / 3) / 3) * 9 + (j % 3) * 3 + (2 * w + j / 3) % 3;
+  return w < 3 ? 18 + 3 * w + 2 : 27;
+}
+constexpr bool sg_wg3l_taps_cover(bool ru) {
+  int seen[28] = {};
+  for (int w = 0; w < 4; ++w)
+    for (int j = 0; j < 7; ++j) ++seen[sg_wg3l_tap(ru, w, j)];
+  for (int t = 0; t < 28; ++t)
+    if (seen[t] != 1) return false;
+  return sg_wg3l_tap(ru, 3, 6) == 27;
+}
+static_assert(sg_wg3l_taps_cover(false) && sg_wg3l_taps_cover(true), "every tap in exactly one slot; wave 3's slot 6 spare");
+
+template <bool UPS, bool DYM = false, int TW = 32, bool M16 = false, bool RU = false>   // UPS: x is the half-resolution tensor, gathered nearest-x2 (upscale3d fused into
                                         // the layer); DYM: dy is the half-resolution gradient of a pooled layer, gathered
                                         // nearest-x2, scaled and LeakyReLU-masked while it is staged; TW = 16: the 16-wide levels
                                         // (4 x 16 x 16) in tiles of 2 x 8 x 16 voxels, halo planes of 10 x 18 rows; M16: the
-                                        // K loop on v_mfma_f32_16x16x32_bf16 (sg_wgrad_tile_lean16)
+                                        // K loop on v_mfma_f32_16x16x32_bf16 (sg_wgrad_tile_lean16); RU: tap columns per wave
+                                        // (sg_wg3l_tap), every halo row read once per column (sg_wgrad_tile_reuse / _reuse16)
 __global__ __launch_bounds__(512) void conv_wgrad3l_kernel(WgradArgs a) {
   static_assert(!(UPS && DYM), "one gathered operand at a time");
   static_assert(TW == 32 || TW == 16, "tile width");
@@ -1353,11 +1570,14 @@ __global__ __launch_bounds__(512) void conv_wgrad3l_kernel(WgradArgs a) {
   int tap_hw[MAXT], tap_kd[MAXT];
 #pragma unroll
   for (int j = 0; j < MAXT; ++j) {
-    const int tap = wave + 4 * j;
+    const int tap = sg_wg3l_tap(RU, wave, j);
     const int kw_i = tap % 3, kh_i = (tap / 3) % 3, kd_i = tap / 9;
     tap_hw[j] = tap < TAPS ? (kh_i * HW + kw_i) * 64 : 0;
     tap_kd[j] = tap < TAPS ? kd_i : 0;
   }
+  // (row reuse) the wave's two tap columns c = kd * 3 + kw: slots 0-2 and 3-5 are their kh = 0 taps' bases + kh * HW * 64
+  const int colA = 2 * wave, colB = 2 * wave + 1;
+  const int col_kd[2] = {colA / 3, colB / 3}, col_kw[2] = {(colA % 3) * 64, (colB % 3) * 64};
   // bias gradient: wave 3's last slot is spare (27 = 4*7 - 1 taps); it multiplies dy by ones
   const int ones_last = (a.dbias != nullptr && ci_t == 0 && wave == 3) ? 1 : 0;
   // 16 accumulator registers per tap: one 32 x 32 tile, or four 16 x 16 tiles [ci half * 2 + co half]
@@ -1376,17 +1596,29 @@ __global__ __launch_bounds__(512) void conv_wgrad3l_kernel(WgradArgs a) {
       a.dbg[grp * 128 + dbgi] = __builtin_amdgcn_s_memtime();
     ++dbgi;
   };
-  typedef typename std::conditional<M16, sg_wgrad_tile_lean16<5, TW>, sg_wgrad_tile_lean<5, TW>>::type KT;
+  constexpr bool ROWS1 = RU && (!M16 || TW == 32);                // the row-reuse K loops (16x16x32 on 16-wide tiles: the tap table only)
+  typedef typename std::conditional<M16, typename std::conditional<ROWS1, sg_wgrad_tile_reuse16<5>, sg_wgrad_tile_lean16<5, TW>>::type,
+                                    typename std::conditional<RU, sg_wgrad_tile_reuse<5, TW>, sg_wgrad_tile_lean<5, TW>>::type>::type KT;
   auto mfma_phase = [&](int q) {
     const int dq = q % nTd;
     const int pbase = 2 * dq - 1 + 8;                             // plane of halo index 0 (kept non-negative)
     typename KT::Ctx c;
     c.yb = yl0;
+    if constexpr (ROWS1) {
 #pragma unroll
-    for (int td = 0; td < 2; ++td)
+      for (int td = 0; td < 2; ++td) {
 #pragma unroll
-      for (int j = 0; j < MAXT; ++j) c.xb[td][j] = xl0 + ((pbase + td + tap_kd[j]) & 3) * PB + tap_hw[j];
-    if (ones_last) c.xb[0][MAXT - 1] = c.xb[1][MAXT - 1] = ONES_OFF + (xl0 - xmine);
+        for (int s = 0; s < 2; ++s) c.xb[td][s] = xl0 + ((pbase + td + col_kd[s]) & 3) * PB + col_kw[s];
+        c.xb[td][2] = xl0 + ((pbase + td + tap_kd[MAXT - 1]) & 3) * PB + tap_hw[MAXT - 1];
+      }
+      if (ones_last) c.xb[0][2] = c.xb[1][2] = ONES_OFF + (xl0 - xmine);
+    } else {
+#pragma unroll
+      for (int td = 0; td < 2; ++td)
+#pragma unroll
+        for (int j = 0; j < MAXT; ++j) c.xb[td][j] = xl0 + ((pbase + td + tap_kd[j]) & 3) * PB + tap_hw[j];
+      if (ones_last) c.xb[0][MAXT - 1] = c.xb[1][MAXT - 1] = ONES_OFF + (xl0 - xmine);
+    }
     KT::run(c, acc);
   };
   const bool stage_first_only = (a.dbg_flags & 1) != 0;
@@ -1463,7 +1695,7 @@ __global__ __launch_bounds__(512) void conv_wgrad3l_kernel(WgradArgs a) {
     }
 #pragma unroll
     for (int j = 0; j < MAXT; ++j) {
-      const int tap = wave + 4 * j;
+      const int tap = sg_wg3l_tap(RU, wave, j);
       if (tap < TAPS && (items_mine > 0 || a.slab != 0)) {
         float* dst = a.dwt + (int64_t)blockIdx.x * a.slab + ((((int64_t)tap * a.ciT + ci_t) * a.coT + co_t) << 10);
 #pragma unroll
@@ -1479,7 +1711,7 @@ __global__ __launch_bounds__(512) void conv_wgrad3l_kernel(WgradArgs a) {
       sg_wg_out(a.dbias + (int64_t)blockIdx.x * a.bslab + co_t * 32 + r, acc[MAXT - 1][0], a.slab != 0);
 #pragma unroll
     for (int j = 0; j < MAXT; ++j) {
-      const int tap = wave + 4 * j;
+      const int tap = sg_wg3l_tap(RU, wave, j);
       if (tap < TAPS && (items_mine > 0 || a.slab != 0)) {
         float* dst = a.dwt + (int64_t)blockIdx.x * a.slab + ((((int64_t)tap * a.ciT + ci_t) * a.coT + co_t) << 10);
 #pragma unroll
@@ -1539,19 +1771,20 @@ static int launch_wgrad3(WgradArgs& a, const sg_conv_shape* s, hipStream_t st, b
   if (lean16 || lean) a.nslab = gx;                   // (the lean kernels add their two groups' sums before they leave the block)
   if (lean) lds += 12288;                             // (+ the lean kernels' image of ones, behind the staging buffers)
   const bool m16 = sg_cfg().wgrad3l_16 != 0;      // the K loop on v_mfma_f32_16x16x32_bf16
+  const bool ru = sg_cfg().wgrad3l_reuse != 0;    // tap columns per wave, every halo row read once per column
+#define SG_LAUNCH_WGRAD3L_1(UPS_, DYM_, TW_, M16_, RU_, NAME_)                                                        \
+  do {                                                                                                               \
+    auto kern = conv_wgrad3l_kernel<UPS_, DYM_, TW_, M16_, RU_>;                                                     \
+    SG_ALLOW_160K_LDS(kern);                                                                                         \
+    SG_KNAME(NAME_);                                                                                                 \
+    hipLaunchKernelGGL(kern, dim3((unsigned)gx, (unsigned)pairs), dim3(512), lds, st, a);                            \
+  } while (0)
 #define SG_LAUNCH_WGRAD3L(UPS_, DYM_, TW_, NAME_)                                                                     \
   do {                                                                                                               \
-    if (m16) {                                                                                                       \
-      auto kern = conv_wgrad3l_kernel<UPS_, DYM_, TW_, true>;                                                        \
-      SG_ALLOW_160K_LDS(kern);                                                                                       \
-      SG_KNAME(NAME_);                                                                                               \
-      hipLaunchKernelGGL(kern, dim3((unsigned)gx, (unsigned)pairs), dim3(512), lds, st, a);                          \
-    } else {                                                                                                         \
-      auto kern = conv_wgrad3l_kernel<UPS_, DYM_, TW_, false>;                                                       \
-      SG_ALLOW_160K_LDS(kern);                                                                                       \
-      SG_KNAME(NAME_);                                                                                               \
-      hipLaunchKernelGGL(kern, dim3((unsigned)gx, (unsigned)pairs), dim3(512), lds, st, a);                          \
-    }                                                                                                                \
+    if (m16 && ru) SG_LAUNCH_WGRAD3L_1(UPS_, DYM_, TW_, true, true, NAME_);                                          \
+    else if (m16) SG_LAUNCH_WGRAD3L_1(UPS_, DYM_, TW_, true, false, NAME_);                                          \
+    else if (ru) SG_LAUNCH_WGRAD3L_1(UPS_, DYM_, TW_, false, true, NAME_);                                           \
+    else SG_LAUNCH_WGRAD3L_1(UPS_, DYM_, TW_, false, false, NAME_);                                                  \
   } while (0)
   if (lean16) {        // (halo plane slots of 208 rows like the 32-wide kernel's)
     lds = 2ull * (4 * 208 * 64 + 256 * 64) + 12288;   // (+ the image of ones)
@@ -1565,6 +1798,7 @@ static int launch_wgrad3(WgradArgs& a, const sg_conv_shape* s, hipStream_t st, b
   } else if (lean) {
     SG_LAUNCH_WGRAD3L(false, false, 32, "conv_wgrad3l");
 #undef SG_LAUNCH_WGRAD3L
+#undef SG_LAUNCH_WGRAD3L_1
   } else {
     auto kern = conv_wgrad3_kernel<KD, KH, KW>;
     SG_ALLOW_160K_LDS(kern);
