@@ -653,6 +653,21 @@ size_t sg_pairwise_sqdist_workspace(int32_t ma, int32_t mb, int64_t v);
 int sg_pairwise_sqdist(const float* a, const float* b, double* out, int32_t ma, int32_t mb, int64_t v, void* workspace,
                        size_t workspace_bytes, sg_stream_t st);
 
+/* ---- batches from a device-resident table (csrc/deck.hip; dataset.ResidentLoader) ----------------------------
+ * table [rows, row_elems] of the source type sdt, row-major, contiguous, on the device (a phase's `.npy` volumes in the files'
+ * own dtype, or the f32 label table); idx: DEVICE int32[n]; out: DEVICE f32 [n, row_elems]:
+ *   out[i][e] = f32(table[idx[i]][e])                         (every source type converts exactly)
+ *   normalise != 0: (f32(table[idx[i]][e]) - mean) / stddev   two correctly rounded f32 operations, no reciprocal, no fused
+ *                                                            form: the bits of np.subtract / np.divide with np.float32 scalars
+ * One launch.  Row offsets are 64-bit (rows * row_elems * element size may pass 4 GiB).  16-byte loads and stores when table,
+ * out and the row length in bytes are multiples of 16, an element path otherwise -- chosen per launch.  An index outside
+ * [0, rows) fills its output row with quiet NaN and the table is not read for it: nothing out of bounds can be read.
+ * SG_EINVAL before any launch: a NULL pointer, rows < 0, row_elems < 1, n < 0, an unknown sdt.  SG_EALIGN: table not aligned to
+ * its element size, idx or out not 4-byte aligned.  n == 0: SG_OK, nothing launched. */
+typedef enum { SG_SRC_U8 = 0, SG_SRC_I8 = 1, SG_SRC_I16 = 2, SG_SRC_U16 = 3, SG_SRC_F16 = 4, SG_SRC_F32 = 5 } sg_src_dtype;
+int sg_gather_rows(const void* table, sg_src_dtype sdt, int64_t rows, int64_t row_elems, const int32_t* idx, int32_t n, float* out,
+                   int32_t normalise, float mean, float stddev, sg_stream_t st);
+
 /* ---- opt-in kernel timing (used by bench.py's roofline leg) ------------------------------------- */
 /* When enabled, every sg_conv3d_fwd / sg_conv3d_wgrad launch is bracketed by hipEvents on its stream.
  * sg_prof_collect synchronises those events and returns, per kind (0 = conv fwd, 1 = wgrad) and per

@@ -16,6 +16,10 @@
   after slot (np.load straight into the pinned buffer, normalise in place, `hipMemcpyAsync` on a side stream); a
   slot is reused only after an event recorded on the CONSUMER's stream, once the consumer has moved on to the next
   batch, has completed -- the step that reads a batch can never see it overwritten.
+* `DeviceTable` / `ResidentLoader` (not in the reference; --device_dataset_gib): the phase's whole table loaded
+  once into device memory in the files' own dtype; a batch is then the drawn positions (N int32 through a pinned ring) and one
+  launch of `sg_gather_rows` on the caller's stream -- no worker thread, no per-step volume copy.  Same deck, same draws, same
+  partition, same label rows, the same f32 bits as the prefetcher.  `make_loader` picks between the two per phase.
 """
 import glob
 import os
@@ -205,17 +209,24 @@ class NumpyPathDataset:
 
     def _drawn(self, positions):
         self.last_labels = None if self.labels is None else self.labels[positions]
-        return [self.scratch_files[i] for i in positions]
+        return positions
 
-    def batch_paths(self, batch_size, auto_repeat=True):
+    def batch_positions(self, batch_size, auto_repeat=True):
+        """The next batch as positions into the file table (what batch_paths names)."""
         return self._drawn(self._deck.draw(batch_size, auto_repeat))
 
-    def batch_mpi_paths(self, batch_size, auto_repeat=True):
+    def batch_mpi_positions(self, batch_size, auto_repeat=True):
         """This rank's share of the next global batch: entries rank, rank + world, ... of the drawn positions (column
         `rank` of the reference's reshape(-1, world) before its scatter; a short last draw gives the low ranks one
         more sample, which is what padding with None and stripping it per rank did, dataset.py:316-338)."""
         drawn = self._deck.draw(batch_size * self.world_size, auto_repeat)
         return self._drawn(drawn[self.rank::self.world_size])
+
+    def batch_paths(self, batch_size, auto_repeat=True):
+        return [self.scratch_files[i] for i in self.batch_positions(batch_size, auto_repeat)]
+
+    def batch_mpi_paths(self, batch_size, auto_repeat=True):
+        return [self.scratch_files[i] for i in self.batch_mpi_positions(batch_size, auto_repeat)]
 
     # ---- materialising ------------------------------------------------------------------------------------
     def load_into(self, paths, out):
@@ -372,3 +383,156 @@ class PinnedPrefetcher:
         if self.cuda:
             self.torch.cuda.current_stream(self.device).synchronize()
         self.slots = []
+
+
+# ---- the phase's table resident on the device (not in the reference; --device_dataset_gib) ----------------------
+_RESIDENT_DTYPES = ('uint8', 'int8', 'int16', 'uint16', 'float16', 'float32')      # what sg_gather_rows reads
+
+
+def _stored_dtype(dtype):
+    """The dtype a file's values are held in: their own where the gather kernel reads it, float32 otherwise (f64, i32, ...:
+    the conversion np.copyto(..., casting='unsafe') makes in load_into, made once at load)."""
+    dtype = np.dtype(dtype)
+    return dtype if dtype.name in _RESIDENT_DTYPES and dtype.isnative else np.dtype(np.float32)
+
+
+class DeviceTable:
+    """Every file of `dataset`, loaded once: `volumes` [F, 1, Z, Y, X] in the files' dtype (logical C order) and `labels`
+    f32 [F, L] or None, on `device`.  The load goes through two pinned staging buffers of STAGING_BYTES / 2 with asynchronous
+    copies: while one is on its way to the device the other is filled."""
+    STAGING_BYTES = 64 << 20
+
+    @staticmethod
+    def estimate_bytes(dataset):
+        """Device bytes of the table, from the dataset's probe alone (shape, dtype, len): nothing is loaded."""
+        if not len(dataset):
+            return 0
+        vol = int(np.prod(dataset.shape, dtype=np.int64)) * _stored_dtype(dataset.dtype).itemsize
+        return len(dataset) * vol + (0 if dataset.labels is None else int(dataset.labels.nbytes))
+
+    def __init__(self, dataset, device='cuda'):
+        import torch
+        if not len(dataset):
+            raise ValueError(f'the dataset {dataset.scratch_dir} holds no files')
+        self.device = torch.device(device)
+        cuda = self.device.type == 'cuda'
+        files, shape, fdtype = list(dataset.scratch_files), tuple(dataset.shape[1:]), np.dtype(dataset.dtype)
+        stored = _stored_dtype(fdtype)
+        tdtype = getattr(torch, stored.name)
+        nfiles, vol = len(files), int(np.prod(shape, dtype=np.int64))
+        flat = torch.empty((nfiles, vol), dtype=tdtype, device=self.device)
+
+        def fill(rows, lo, hi):      # files [lo, hi) into the rows of a host array
+            for k, path in enumerate(files[lo:hi]):
+                a = np.load(path)
+                if tuple(a.shape) != shape or a.dtype != fdtype:
+                    raise ValueError(f'{path} holds {a.dtype} {tuple(a.shape)}, but the first file of the table, {files[0]}, '
+                                     f'holds {fdtype} {shape}: a resident table needs one shape and one dtype')
+                np.copyto(rows[k].reshape(shape), a, casting='unsafe')      # (logical order: a Fortran-ordered file too)
+
+        if cuda:
+            per = max(1, min(nfiles, (self.STAGING_BYTES // 2) // max(1, vol * stored.itemsize)))
+            halves = [torch.empty((per, vol), dtype=tdtype, pin_memory=True) for _ in range(2 if nfiles > per else 1)]
+            done = [None] * len(halves)
+            stream = torch.cuda.current_stream(self.device)
+            for c, lo in enumerate(range(0, nfiles, per)):
+                h, hi = c % len(halves), min(nfiles, lo + per)
+                if done[h] is not None:
+                    done[h].synchronize()      # the copy that read this half has finished
+                fill(halves[h].numpy(), lo, hi)
+                flat[lo:hi].copy_(halves[h][:hi - lo], non_blocking=True)
+                done[h] = torch.cuda.Event()
+                done[h].record(stream)
+            stream.synchronize()      # the staging buffers go away with this frame
+        else:
+            fill(flat.numpy(), 0, nfiles)
+        self.volumes = flat.view((nfiles, 1) + shape)
+        self.labels = None if dataset.labels is None else torch.from_numpy(np.ascontiguousarray(dataset.labels)).to(self.device)
+        self.nbytes = flat.numel() * flat.element_size() + (0 if self.labels is None else self.labels.numel() * 4)
+
+    def __len__(self):
+        return self.volumes.shape[0]
+
+
+class ResidentLoader:
+    """PinnedPrefetcher's surface -- next(), .labels, close() -- over a DeviceTable, without a worker thread.  next() draws
+    the batch's positions, writes them into one slot of a ring of pinned int32 buffers, copies the slot to the device on the
+    caller's stream and launches the gather (and a second one for the label rows) into one of THREE output buffers.  Everything
+    is ordered by that stream: the tensor next() returns stays valid until the call after the next one, as the prefetcher's
+    does.  A pinned slot is written again only after the copy that read it has completed (an event per slot)."""
+    OUTPUTS, INDEX_SLOTS = 3, 4
+
+    def __init__(self, dataset, batch_size, distributed, mean=None, stddev=None, device='cuda', table=None):
+        import torch
+        from . import functional
+        self.torch, self.F = torch, functional
+        self.ds, self.bs, self.dist = dataset, int(batch_size), bool(distributed)
+        normalise = _norm_args(mean, stddev, 'normalizing') if (mean is not None or stddev is not None) else False
+        self.mean, self.std = (np.float32(mean), np.float32(stddev)) if normalise else (None, None)
+        self.table = table if table is not None else DeviceTable(dataset, device)
+        self.device = self.table.device
+        self.cuda = self.device.type == 'cuda'
+        self.labels = None                            # label rows of the batch next() returned last (device, [N, L])
+        self.calls = 0
+        if self.cuda:
+            f32 = dict(dtype=torch.float32, device=self.device)
+            self.out = [torch.empty((self.bs,) + tuple(self.table.volumes.shape[1:]), **f32) for _ in range(self.OUTPUTS)]
+            self.lab_out = None if self.table.labels is None else \
+                [torch.empty((self.bs, self.table.labels.shape[1]), **f32) for _ in range(self.OUTPUTS)]
+            self.idx_host = torch.empty((self.INDEX_SLOTS, self.bs), dtype=torch.int32, pin_memory=True)
+            self.idx_np = self.idx_host.numpy()
+            self.idx_dev = torch.empty((self.INDEX_SLOTS, self.bs), dtype=torch.int32, device=self.device)
+            self.copied = [None] * self.INDEX_SLOTS
+
+    def next(self):
+        torch, F = self.torch, self.F
+        drawn = self.ds.batch_mpi_positions(self.bs) if self.dist else self.ds.batch_positions(self.bs)
+        pos = F.check_positions(np.asarray(drawn, dtype=np.int64), len(self.table))
+        n = pos.shape[0]
+        if not self.cuda:
+            self.labels = None if self.table.labels is None else F.gather_rows(self.table.labels, pos)
+            self.calls += 1
+            return F.gather_rows(self.table.volumes, pos, self.mean, self.std)
+        s, k = self.calls % self.INDEX_SLOTS, self.calls % self.OUTPUTS
+        self.calls += 1
+        if self.copied[s] is None:
+            self.copied[s] = torch.cuda.Event()
+        else:
+            self.copied[s].synchronize()      # the copy that read this pinned slot INDEX_SLOTS calls ago
+        self.idx_np[s, :n] = pos
+        idx = self.idx_dev[s, :n]
+        idx.copy_(self.idx_host[s, :n], non_blocking=True)
+        self.copied[s].record(torch.cuda.current_stream(self.device))
+        out = F.gather_rows(self.table.volumes, idx, self.mean, self.std, out=self.out[k][:n])
+        if self.lab_out is not None:
+            self.labels = F.gather_rows(self.table.labels, idx, out=self.lab_out[k][:n])
+        return out
+
+    def close(self):
+        if self.cuda:
+            self.torch.cuda.current_stream(self.device).synchronize()
+            self.out = self.lab_out = self.idx_dev = self.idx_host = self.idx_np = None
+        self.table = None
+
+
+def make_loader(dataset, batch_size, distributed, mean=None, stddev=None, device='cuda', budget_gib=0.0):
+    """The phase's loader: a ResidentLoader when `budget_gib` (per process; 0 = off) is positive and the table's
+    DeviceTable.estimate_bytes fits it, otherwise -- also when the allocation fails -- a PinnedPrefetcher, with one notice line
+    that gives both figures."""
+    budget = int(float(budget_gib or 0.0) * 2 ** 30)
+    if float(budget_gib or 0.0) > 0 and len(dataset):
+        need = DeviceTable.estimate_bytes(dataset)
+        if need <= budget:
+            try:
+                table = DeviceTable(dataset, device)
+            except (MemoryError, RuntimeError) as e:
+                if not isinstance(e, MemoryError) and 'out of memory' not in str(e).lower():
+                    raise
+                print(f"INFO: device dataset: allocating the {need} byte table of {dataset.scratch_dir} failed (budget {budget} "
+                      f"bytes): streaming this phase from the host")
+            else:
+                return ResidentLoader(dataset, batch_size, distributed, mean, stddev, device, table=table)
+        else:
+            print(f"INFO: device dataset: the table of {dataset.scratch_dir} needs {need} bytes, the budget is {budget} bytes "
+                  f"({float(budget_gib)} GiB): streaming this phase from the host")
+    return PinnedPrefetcher(dataset, batch_size, distributed, mean, stddev, device)

@@ -2517,3 +2517,66 @@ def guard_step_(flag, t, counters, lr, lr_t, adam=None, lr_dev=None):
     b1, b2 = adam if adam is not None else (0.0, 0.0)
     check(lib.sg_guard_step(_ptr(flag), _ptr(t), _ptr(counters), float(lr), None if lr_dev is None else _dev_ptr(lr_dev),
                             _ptr(lr_t), 1 if adam is not None else 0, float(b1), float(b2), _stream()), 'sg_guard_step')
+
+
+# ---- batches from a resident table (dataset.ResidentLoader): out[i] = f32(table[idx[i]]), optionally normalised
+_SRC_DT = {torch.uint8: _lib.SG_SRC_U8, torch.int8: _lib.SG_SRC_I8, torch.int16: _lib.SG_SRC_I16, torch.uint16: _lib.SG_SRC_U16,
+           torch.float16: _lib.SG_SRC_F16, torch.float32: _lib.SG_SRC_F32}
+
+
+def check_positions(positions, rows):
+    """Host table positions as a contiguous int32 array; ValueError if one lies outside [0, rows).  (The kernel guards itself
+    as well -- such a row comes back as NaN -- but a bad draw is a bug of the caller's and is reported where it is made.)"""
+    import numpy as np
+    pos = np.ascontiguousarray(positions.numpy() if torch.is_tensor(positions) else positions)
+    if pos.ndim != 1 or (pos.size and not np.issubdtype(pos.dtype, np.integer)):
+        raise ValueError(f'gather_rows: expected a 1-D sequence of integer positions, got {pos.dtype} {pos.shape}')
+    if pos.size and (int(pos.min()) < 0 or int(pos.max()) >= rows):
+        bad = int(pos[(pos < 0) | (pos >= rows)][0])
+        raise ValueError(f'gather_rows: position {bad} lies outside the table of {rows} rows')
+    return pos.astype(np.int32, copy=False)
+
+
+def gather_rows(table, idx, mean=None, stddev=None, out=None):
+    """f32 [n, ...] = the rows idx of table [rows, ...] (u8 / i8 / i16 / u16 / f16 / f32), converted exactly and, with mean and
+    stddev, normalised as (x - mean) / stddev in two correctly rounded f32 operations: the bits np.subtract / np.divide with
+    np.float32 scalars give (sg_gather_rows, one launch).  idx: host positions (a sequence, an array or a CPU tensor: validated,
+    then uploaded) or an int32 tensor on the table's device (used as it is: a position outside the table gives a NaN row).
+    out: an f32 buffer of the result's shape to write into.  A CPU table takes the same two numpy operations in the same order."""
+    if (mean is None) != (stddev is None):
+        raise ValueError('gather_rows: give both mean and stddev, or neither')
+    if table.dtype not in _SRC_DT:
+        raise TypeError(f'gather_rows: tables are uint8, int8, int16, uint16, float16 or float32, got {table.dtype}')
+    if table.dim() < 1 or not table.is_contiguous():
+        raise ValueError('gather_rows: expected a contiguous [rows, ...] table')
+    rows = table.shape[0]
+    on_device = torch.is_tensor(idx) and idx.is_cuda
+    if on_device:
+        if not table.is_cuda or idx.device != table.device or idx.dtype != torch.int32 or idx.dim() != 1 or not idx.is_contiguous():
+            raise ValueError('gather_rows: device positions are a contiguous 1-D int32 tensor on the table\'s device')
+    else:
+        pos = check_positions(idx, rows)
+    n = idx.shape[0] if on_device else pos.shape[0]
+    shape = (n,) + tuple(table.shape[1:])
+    if out is not None and (tuple(out.shape) != shape or out.dtype != torch.float32 or out.device != table.device
+                            or not out.is_contiguous()):
+        raise ValueError(f'gather_rows: out must be a contiguous float32 {shape} tensor on {table.device}')
+    if not table.is_cuda:
+        import numpy as np
+        res = np.empty(shape, dtype=np.float32)
+        np.copyto(res, table.numpy()[pos], casting='unsafe')
+        if mean is not None:
+            np.subtract(res, np.float32(mean), out=res)
+            np.divide(res, np.float32(stddev), out=res)
+        res = torch.from_numpy(res)
+        return res if out is None else out.copy_(res)
+    lib = _lib.load()
+    if not on_device:
+        idx = torch.from_numpy(pos).to(table.device)
+    if out is None:
+        out = torch.empty(shape, device=table.device, dtype=torch.float32)
+    row_elems = table.numel() // rows if rows else max(1, math.prod(table.shape[1:]))
+    check(lib.sg_gather_rows(_ptr(table), _SRC_DT[table.dtype], rows, row_elems, _ptr(idx), n, _ptr(out),
+                             0 if mean is None else 1, 0.0 if mean is None else float(mean), 1.0 if mean is None else float(stddev),
+                             _stream()), 'sg_gather_rows')
+    return out

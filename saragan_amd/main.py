@@ -66,6 +66,11 @@ def build_parser():
                    help='(not in the reference) always replay the training step as one hipGraph (SARAGAN_HIPGRAPH=1); by default a '
                         'phase is captured when its steps measure host-bound')
     p.add_argument('--no_hipgraph', default=False, action='store_true', help='(not in the reference) never capture: SARAGAN_HIPGRAPH=0')
+    p.add_argument('--device_dataset_gib', type=float, default=0.0,
+                   help='(not in the reference) keep a phase\'s whole .npy table in device memory, in the files\' dtype, and gather '
+                        'each batch with one kernel launch instead of loading it through the host, when the table fits G GiB; '
+                        '0 = off.  The budget is PER PROCESS: under --horovod every rank holds the whole table.  Decided per '
+                        'phase: a phase whose table does not fit is streamed from the host as before.  DESIGN.md section 4.6')
     p.add_argument('--skip_nonfinite_steps', default=False, action='store_true',
                    help='(not in the reference) skip a network\'s update, on the device, when its gradient holds a NaN or Inf '
                         '(saragan_amd.set_nonfinite_guard); the skip counts are printed on a line of their own at each log point')

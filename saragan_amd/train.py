@@ -16,7 +16,7 @@ import torch
 from . import optimization as opt
 from . import parallel
 from .ExtendedEMA import ExtendedEMA
-from .dataset import NumpyPathDataset, PinnedPrefetcher, normalize_numpy
+from .dataset import NumpyPathDataset, make_loader, normalize_numpy
 from .metrics.save_metrics import get_compute_metrics_dict, save_metrics
 from .networks import loss as L
 from .networks import ops as nops
@@ -231,7 +231,9 @@ def _run_training(args, device, max_steps_per_phase, log_every):
         if horovod:
             parallel.broadcast_global_variables(store, 0)
 
-        loader = PinnedPrefetcher(npy_data, batch_size, horovod, args.data_mean, args.data_stddev, device)  # quirk Q3
+        # quirk Q3.  (not in the reference) --device_dataset_gib: the phase's table resident on the device when it fits the budget
+        loader = make_loader(npy_data, batch_size, horovod, args.data_mean, args.data_stddev, device,
+                             getattr(args, 'device_dataset_gib', 0.0))
         local_step = 0
         mixing_bool = args.mixing_nimg > 0
         t_phase, imgs, d_loss, g_loss = time.time(), 0, float('nan'), float('nan')
