@@ -47,10 +47,18 @@ def wgrad_ref(x, dy, k, ups=False):
     xp[:, pd:pd + d, ph:ph + h, pw:pw + w] = x.permute(0, 2, 3, 4, 1)
     dyv = dy.permute(0, 2, 3, 4, 1).reshape(-1, cout)
     dw = torch.empty((k[0], k[1], k[2], cin, cout), dtype=torch.float64, device=x.device)
+    # (a product that reduces over 2^18 .. 2^20 voxels into 32 x 64 outputs keeps a GPU's fp64 GEMM on a handful of tiles: the
+    # voxels are cut into up to 256 equal slabs, one batched product, and the slabs summed -- the same exact value)
+    nvox = dyv.shape[0]
+    slabs = 1
+    while slabs < 256 and nvox % (2 * slabs) == 0 and nvox // (2 * slabs) >= 1024:
+        slabs *= 2
+    dys = dyv.reshape(slabs, -1, cout)
     for a in range(k[0]):
         for b in range(k[1]):
             for c in range(k[2]):
-                dw[a, b, c] = xp[:, a:a + d, b:b + h, c:c + w].reshape(-1, cin).t() @ dyv
+                xs = xp[:, a:a + d, b:b + h, c:c + w].reshape(slabs, -1, cin)
+                dw[a, b, c] = torch.bmm(xs.transpose(1, 2), dys).sum(0)
     return dw, dyv.sum(0)
 
 
