@@ -663,10 +663,33 @@ int sg_pairwise_sqdist(const float* a, const float* b, double* out, int32_t ma, 
  * out and the row length in bytes are multiples of 16, an element path otherwise -- chosen per launch.  An index outside
  * [0, rows) fills its output row with quiet NaN and the table is not read for it: nothing out of bounds can be read.
  * SG_EINVAL before any launch: a NULL pointer, rows < 0, row_elems < 1, n < 0, an unknown sdt.  SG_EALIGN: table not aligned to
- * its element size, idx or out not 4-byte aligned.  n == 0: SG_OK, nothing launched. */
-typedef enum { SG_SRC_U8 = 0, SG_SRC_I8 = 1, SG_SRC_I16 = 2, SG_SRC_U16 = 3, SG_SRC_F16 = 4, SG_SRC_F32 = 5 } sg_src_dtype;
+ * its element size, idx or out not 4-byte aligned.  n == 0: SG_OK, nothing launched.
+ * SG_SRC_BF16 is read by sg_intensity_hist only: sg_gather_rows answers it with SG_EINVAL, as it does every unknown sdt. */
+typedef enum { SG_SRC_U8 = 0, SG_SRC_I8 = 1, SG_SRC_I16 = 2, SG_SRC_U16 = 3, SG_SRC_F16 = 4, SG_SRC_F32 = 5, SG_SRC_BF16 = 6 } sg_src_dtype;
 int sg_gather_rows(const void* table, sg_src_dtype sdt, int64_t rows, int64_t row_elems, const int32_t* idx, int32_t n, float* out,
                    int32_t normalise, float mean, float stddev, sg_stream_t st);
+
+/* ---- voxel-intensity histograms (csrc/hist.hip; metrics/intensity_metrics.py) --------------------------------
+ * x [rows, row_elems] of the source type dt (any sg_src_dtype, SG_SRC_BF16 included), row-major, contiguous, on the device;
+ * out: DEVICE int64 [rows][bins + 1].  Per element, in f32 and exactly:
+ *   t = x * scale + shift          two correctly rounded operations, never fused: numpy's x * np.float32(scale) + np.float32(shift)
+ *   column = bins                  where t is NaN (the extra column)
+ *            bins - 1              where t >= lo + bins (saturated: +inf too)
+ *            0                     where t <  lo        (saturated: -inf too)
+ *            min(floor(t) - lo, bins - 1) otherwise
+ * Both saturation tests are float comparisons made before any conversion.  The top edge is closed: the last bin holds hi - 1
+ * and hi = lo + bins, as np.histogram(bins = hi - lo, range = (lo, hi)) does.  Every row of `out` grows by row_elems.
+ * accumulate == 0: out is zeroed on the stream first; != 0: the counts are added to what is there.  rows = 1 with
+ * row_elems = n * v is the pooled histogram of a batch.  Counts are integers added with atomics: the result does not depend
+ * on the order, two calls give the same tensor.  Every offset is 64-bit.  x need only be aligned to its element size
+ * (16-byte loads from the first 16-byte boundary of every chunk, an element path in front of it and behind the last whole
+ * load).
+ * SG_EINVAL before any launch: bins < 1, bins > sg_intensity_hist_max_bins(), rows < 0, row_elems < 0, scale not finite,
+ * an unknown dt, lo + bins > 2147483520 (the largest int32 an f32 holds), a NULL pointer with work to do.  SG_EALIGN: x not aligned to its element size, out
+ * not 8-byte aligned.  rows == 0: SG_OK, nothing launched; row_elems == 0: only the zeroing. */
+int32_t sg_intensity_hist_max_bins(void);      /* the LDS image of a block: 8191 */
+int sg_intensity_hist(const void* x, sg_src_dtype dt, int64_t rows, int64_t row_elems, float scale, float shift, int32_t lo,
+                      int32_t bins, int64_t* out, int accumulate, sg_stream_t st);
 
 /* ---- opt-in kernel timing (used by bench.py's roofline leg) ------------------------------------- */
 /* When enabled, every sg_conv3d_fwd / sg_conv3d_wgrad launch is bracketed by hipEvents on its stream.

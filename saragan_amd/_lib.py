@@ -17,8 +17,10 @@ SG_AUG_FLIP_W, SG_AUG_FLIP_H, SG_AUG_FLIP_D, SG_AUG_ROT90, SG_AUG_TRANSLATE, SG_
 # sg_augment_affine_* transform bits (a mask of their own) and apply flags
 SG_AUGF_SCALE, SG_AUGF_ROTATE, SG_AUGF_SHIFT, SG_AUGF_BRIGHTNESS, SG_AUGF_CONTRAST, SG_AUGF_ALL = 32, 64, 128, 256, 512, 992
 SG_AUGF_ADJOINT, SG_AUGF_LINEAR = 1, 2
-# sg_gather_rows source types (sg_src_dtype)
-SG_SRC_U8, SG_SRC_I8, SG_SRC_I16, SG_SRC_U16, SG_SRC_F16, SG_SRC_F32 = 0, 1, 2, 3, 4, 5
+# sg_gather_rows / sg_intensity_hist source types (sg_src_dtype; bf16 is read by the histogram only)
+SG_SRC_U8, SG_SRC_I8, SG_SRC_I16, SG_SRC_U16, SG_SRC_F16, SG_SRC_F32, SG_SRC_BF16 = 0, 1, 2, 3, 4, 5, 6
+# sg_intensity_hist_max_bins(), restated so that argument checks run before the library is loaded (a GPU test compares the two)
+INTENSITY_HIST_MAX_BINS = 8191
 
 
 class ConvShape(C.Structure):
@@ -159,6 +161,8 @@ SIGNATURES = {
     'sg_pairwise_sqdist_workspace': (_sz, [_i32, _i32, _i64]),
     'sg_pairwise_sqdist': (C.c_int, [_p, _p, _p, _i32, _i32, _i64, _p, _sz, _p]),
     'sg_gather_rows': (C.c_int, [_p, C.c_int, _i64, _i64, _p, _i32, _p, _i32, _f, _f, _p]),
+    'sg_intensity_hist_max_bins': (_i32, []),
+    'sg_intensity_hist': (C.c_int, [_p, C.c_int, _i64, _i64, _f, _f, _i32, _i32, _p, C.c_int, _p]),
     'sg_prof_enable': (C.c_int, [C.c_int]),
     'sg_prof_enabled': (C.c_int, []),
     'sg_prof_collect': (C.c_int, [C.POINTER(ProfEntry), _i32, C.POINTER(_i32)]),

@@ -115,6 +115,7 @@ extern "C" int sg_gather_rows(const void* table, sg_src_dtype sdt, int64_t rows,
     case SG_SRC_U16: return dk_launch<uint16_t>(table, rows, row_elems, idx, n, out, normalise, mean, stddev, hs);
     case SG_SRC_F16: return dk_launch<_Float16>(table, rows, row_elems, idx, n, out, normalise, mean, stddev, hs);
     case SG_SRC_F32: return dk_launch<float>(table, rows, row_elems, idx, n, out, normalise, mean, stddev, hs);
+    case SG_SRC_BF16: break;      // sg_intensity_hist's input type, no table type: refused above
   }
   return SG_EINVAL;
 }

@@ -2580,3 +2580,51 @@ def gather_rows(table, idx, mean=None, stddev=None, out=None):
                              0 if mean is None else 1, 0.0 if mean is None else float(mean), 1.0 if mean is None else float(stddev),
                              _stream()), 'sg_gather_rows')
     return out
+
+
+# ---- voxel-intensity histograms (metrics/intensity_metrics.py) ---------------------------------------------------
+_HIST_DT = dict(_SRC_DT)
+_HIST_DT[torch.bfloat16] = _lib.SG_SRC_BF16
+
+
+def intensity_hist(x, lo, hi, scale=1.0, shift=0.0, pooled=False, out=None, accumulate=False):
+    """int64 [rows, hi - lo + 1] counts of x [n, ...] (u8 / i8 / i16 / u16 / f16 / bf16 / f32, contiguous, on the device) in the
+    unit-wide bins of [lo, hi] after t = x * scale + shift, two correctly rounded f32 operations (sg_intensity_hist, one
+    launch): column min(floor(t) - lo, hi - lo - 1), values under lo in the first bin and values from hi on in the last (the top
+    edge is closed), NaN in the extra last column -- so every row sums to its element count.  pooled=False: one row per
+    sample; pooled=True: one row for the whole batch.  out: an int64 buffer of the result's shape; accumulate=True adds to it
+    instead of overwriting it."""
+    if not torch.is_tensor(x):
+        raise TypeError(f'intensity_hist: expected a tensor, got {type(x).__name__}')
+    if x.dtype not in _HIST_DT:
+        raise TypeError(f'intensity_hist: inputs are uint8, int8, int16, uint16, float16, bfloat16 or float32, got {x.dtype}')
+    if x.dim() < 1 or not x.is_contiguous():
+        raise ValueError('intensity_hist: expected a contiguous [n, ...] tensor')
+    lo, hi = int(lo), int(hi)
+    if hi <= lo:
+        raise ValueError(f'intensity_hist: the range [{lo}, {hi}] is empty')
+    bins = hi - lo
+    if bins > _lib.INTENSITY_HIST_MAX_BINS:
+        raise ValueError(f'intensity_hist: {bins} bins, at most {_lib.INTENSITY_HIST_MAX_BINS} fit the kernel\'s LDS image')
+    if lo < -2 ** 31 or hi > 2147483520:      # (the largest int32 a float32 holds)
+        raise ValueError(f'intensity_hist: the range [{lo}, {hi}] does not fit 32-bit integers that float32 can bound')
+    if not math.isfinite(float(scale)):
+        raise ValueError(f'intensity_hist: scale {scale} is not finite')
+    n = x.shape[0]
+    rows, row_elems = (1, x.numel()) if pooled else (n, x.numel() // n if n else math.prod(x.shape[1:]))
+    shape = (rows, bins + 1)
+    if out is None:
+        if accumulate:
+            raise ValueError('intensity_hist: accumulate=True needs the buffer to add to (out)')
+    elif (not torch.is_tensor(out) or tuple(out.shape) != shape or out.dtype != torch.int64 or out.device != x.device
+          or not out.is_contiguous()):
+        raise ValueError(f'intensity_hist: out must be a contiguous int64 {shape} tensor on {x.device}')
+    if not x.is_cuda:
+        raise ValueError('intensity_hist: the input is a device tensor (there is no CPU path)')
+    lib = _lib.load()
+    if out is None:
+        out = torch.empty(shape, device=x.device, dtype=torch.int64)
+    with torch.cuda.device(x.device):
+        check(lib.sg_intensity_hist(_ptr(x), _HIST_DT[x.dtype], rows, row_elems, float(scale), float(shift), lo, bins, _ptr(out),
+                                    1 if accumulate else 0, _stream()), 'sg_intensity_hist')
+    return out

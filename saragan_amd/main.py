@@ -170,6 +170,16 @@ def build_parser():
     p.add_argument('--compute_precision_recall', default=False, action='store_true',
                    help='k-NN precision (fidelity) and recall (coverage: low under mode collapse)')
     p.add_argument('--pr_k', default=3, type=int, help='neighbour rank of the precision / recall radii')
+    # (new flags) voxel-intensity histogram distances in data units, counted on the device: metrics/intensity_metrics.py
+    p.add_argument('--compute_intensity_hist', default=False, action='store_true',
+                   help='KS, Wasserstein-1 and largest density gap between the intensity histograms of reals and fakes; needs '
+                        '--hist_range')
+    p.add_argument('--hist_range', type=none_or_str, default=None,
+                   help='with --compute_intensity_hist: LO,HI in data units (for CT: Hounsfield units as stored), unit-wide bins '
+                        'over [LO, HI]; values outside fall into the first and the last bin.  A negative LO is written '
+                        '--hist_range=LO,HI')
+    p.add_argument('--hist_levels', type=int, default=1,
+                   help='with --compute_intensity_hist: 1 = the volumes; N = plus N - 1 detail levels of the Laplacian pyramid')
     p.add_argument('--dtype', default='bf16', choices=['bf16', 'f32'], help='activation / MFMA input type (new flag)')
     p.add_argument('--max_steps_per_phase', type=int, default=None, help='smoke runs: cap the steps per phase (new flag)')
     return p
@@ -247,6 +257,28 @@ def finalize_mbstd_args(args):
     return args
 
 
+def finalize_hist_args(args):
+    """--compute_intensity_hist: --hist_range 'LO,HI' becomes the tuple (lo, hi); refused at start-up where the run could not
+    use it."""
+    if not getattr(args, 'compute_intensity_hist', False):
+        return args
+    text = getattr(args, 'hist_range', None)
+    if text is None:
+        raise SystemExit('--compute_intensity_hist needs --hist_range LO,HI (the intensity range in data units)')
+    if not isinstance(text, tuple):
+        try:
+            lo, hi = (int(v) for v in str(text).split(','))
+        except ValueError:
+            raise SystemExit(f'--hist_range: expected two integers LO,HI, got {text!r}')
+        from ._lib import INTENSITY_HIST_MAX_BINS
+        if not 1 <= hi - lo <= INTENSITY_HIST_MAX_BINS:
+            raise SystemExit(f'--hist_range: HI - LO must lie in [1, {INTENSITY_HIST_MAX_BINS}], got {lo},{hi}')
+        args.hist_range = (lo, hi)
+    if getattr(args, 'hist_levels', 1) < 1:
+        raise SystemExit('--hist_levels must be >= 1')
+    return args
+
+
 def finalize_args(args):
     """main.py:384-411 post-parse defaults: the discriminator inherits the generator's optimiser settings unless
     the --d_use_different_* switches are given; presets fill missing kernel/filter specs."""
@@ -257,6 +289,7 @@ def finalize_args(args):
             raise SystemExit('--max_consecutive_nonfinite must be >= 1')
     finalize_augment_args(args)
     finalize_mbstd_args(args)
+    finalize_hist_args(args)
     if getattr(args, 'conditioning_path', None) and args.architecture != 'pgan':
         raise SystemExit(f'--conditioning_path is offered for the pgan architecture only, got {args.architecture!r}')
     if getattr(args, 'sn_iterations', 1) != 1 and not getattr(args, 'd_spectral_norm', False):

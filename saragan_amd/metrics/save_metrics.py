@@ -8,7 +8,8 @@ MPI.COMM_WORLD.Gather of the ranks' fake images (save_metrics.py:117-131) is tor
 the Inception graph the reference downloads (metrics/fid_new.py:291-318): --compute_FID is answered with a printed notice at
 every evaluation and no 'FID' key.  In its place (not in the reference): --compute_mmd, --compute_nn_accuracy and
 --compute_precision_recall, three download-free two-sample statistics over the POOLED evaluated batches
-(metrics/sample_metrics.py)."""
+(metrics/sample_metrics.py), and --compute_intensity_hist, the distances of the voxel-intensity histograms in data units
+(metrics/intensity_metrics.py; the reference's metrics/kms.py, which its loop never calls)."""
 import time
 
 import numpy as np
@@ -16,6 +17,7 @@ import torch
 
 from .. import _lib
 from ..dataset import normalize_numpy
+from . import intensity_metrics as IM
 from . import sample_metrics as SM
 from . import skim_metrics as SK
 from . import swd as SWD
@@ -26,7 +28,8 @@ SAMPLE_FLAGS = ('compute_mmd', 'compute_nn_accuracy', 'compute_precision_recall'
 def get_compute_metrics_dict(args):
     """utils.py:267-277."""
     return {k: bool(getattr(args, k, False)) for k in
-            ('compute_FID', 'compute_swds', 'compute_ssims', 'compute_psnrs', 'compute_mses', 'compute_nrmses') + SAMPLE_FLAGS}
+            ('compute_FID', 'compute_swds', 'compute_ssims', 'compute_psnrs', 'compute_mses', 'compute_nrmses') + SAMPLE_FLAGS
+            + ('compute_intensity_hist',)}
 
 
 def _gather_to_rank0(fake, global_size):
@@ -41,7 +44,7 @@ def _gather_to_rank0(fake, global_size):
 
 def save_metrics(writer, sess, npy_data, gen_sample, batch_size, global_size, global_step, imagesize_xy, horovod,
                  hyperparam_opt_inter_trial, compute_metrics, num_metric_samples, data_mean, data_stddev, verbose, suffix='',
-                 keep=None, conditioning=None, pr_k=3, keep_sets=None):
+                 keep=None, conditioning=None, pr_k=3, keep_sets=None, hist_range=None, hist_levels=1, keep_hists=None):
     """Same arguments and return value as the reference (a dict with the keys swd, ssim, psnr, mse, nrmse of the enabled
     metrics).  `keep`: a list that receives (real_batch, fake_batch) of every evaluated batch (tests).  `conditioning` (not in
     the reference): the step graph's label placeholder -- the fakes are generated with the label rows of the real batch they
@@ -49,7 +52,12 @@ def save_metrics(writer, sess, npy_data, gen_sample, batch_size, global_size, gl
     compute_mmd / compute_nn_accuracy / compute_precision_recall (not in the reference; metrics/sample_metrics.py) are set
     statistics: the evaluated batches stay on the device and are evaluated once, pooled, after the loop (keys mmd,
     nn_accuracy[_real|_fake], precision, recall).  `pr_k`: the neighbour rank of precision / recall.  `keep_sets`: a list
-    that receives (n, distance matrix as numpy) when that evaluation ran (tests)."""
+    that receives (n, distance matrix as numpy) when that evaluation ran (tests).
+    compute_intensity_hist (metrics/intensity_metrics.py): every evaluated batch is counted into an IntensityAccumulator over
+    `hist_range` = (lo, hi) in data units -- the batches are normalised, so the kernel maps them back with scale = data_stddev,
+    shift = data_mean (1, 0 for data that is not normalised) -- on `hist_levels` levels; nothing is retained, the distances are
+    read off the counts after the loop (keys intensity_ks, intensity_w1, intensity_gap: a list per level).  `keep_hists`: a
+    list that receives the accumulator's level count and, per batch, the two Laplacian pyramids (tests)."""
     def log(s):
         if verbose:
             print(s)
@@ -70,6 +78,15 @@ def save_metrics(writer, sess, npy_data, gen_sample, batch_size, global_size, gl
     swds_local, psnrs_local, mses_local, nrmses_local, ssims_local = [], [], [], [], []
     pool_sets = any(compute_metrics.get(f) for f in SAMPLE_FLAGS)
     reals_kept, fakes_kept = [], []
+    hist = None
+    if compute_metrics.get('compute_intensity_hist') and rank0:
+        if hist_range is None:
+            raise ValueError('compute_intensity_hist needs hist_range=(lo, hi) in data units (--hist_range LO,HI)')
+        if isinstance(hist_range, str):      # (a namespace that did not go through main.finalize_args)
+            hist_range = IM.parse_range(hist_range)
+        normalised = data_mean is not None and data_stddev is not None
+        hist = IM.IntensityAccumulator(hist_range[0], hist_range[1], data_stddev if normalised else 1.0,
+                                       data_mean if normalised else 0.0, hist_levels)
     counter = 0
     while True:
         real_batch = npy_data.batch_mpi(batch_size) if horovod else npy_data.batch(batch_size)      # :94-97
@@ -112,6 +129,8 @@ def save_metrics(writer, sess, npy_data, gen_sample, batch_size, global_size, gl
             if pool_sets:
                 reals_kept.append(real.reshape(real.shape[0], -1).to(torch.float32))
                 fakes_kept.append(fake.reshape(fake.shape[0], -1).to(torch.float32))
+            if hist is not None:
+                hist.add(real, fake, keep=keep_hists)
             for flag, fn, dest, name in (('compute_swds', SWD.get_swd_for_volumes, swds_local, 'swds'),
                                          ('compute_psnrs', SK.get_psnr, psnrs_local, 'psnrs'),
                                          ('compute_ssims', SK.get_ssim, ssims_local, 'ssims'),
@@ -142,6 +161,13 @@ def save_metrics(writer, sess, npy_data, gen_sample, batch_size, global_size, gl
             log(f"SWDS: {metrics['swd']}")
         if pool_sets:
             metrics.update(_sample_set_metrics(reals_kept, fakes_kept, compute_metrics, pr_k, keep_sets, log))
+        if hist is not None:
+            m = hist.result()
+            if keep_hists is not None:
+                keep_hists.append(hist.levels)
+            for line in IM.format_lines(m):
+                log(line)
+            metrics.update(m)
     return metrics
 
 

@@ -162,18 +162,23 @@ def _run_training(args, device, max_steps_per_phase, log_every):
         metric_tap = getattr(args, '_metric_tap', None)      # tests: receives (tag, metrics dict, batches)
 
         metric_sets = getattr(args, '_metric_sets', None)    # tests: receives (phase, tag, n, distance matrix) per pooled evaluation
+        metric_hists = getattr(args, '_metric_hists', None)  # tests: receives (phase, tag, pyramids of the batches..., levels)
 
         def run_metrics(subset, nsamples, suffix='', tag='loop'):
             kept = [] if metric_tap is not None else None
             sets = [] if metric_sets is not None else None
+            hists = [] if metric_hists is not None else None
             m = save_metrics(None, sess, subset, gen_sample, getattr(args, 'metrics_batch_size', 16), global_size, global_step,
                              get_xy_dim(phase, args.start_shape), horovod, False, metric_flags, nsamples, args.data_mean,
                              args.data_stddev, verbose, suffix=suffix, keep=kept, conditioning=conditioning,
-                             pr_k=getattr(args, 'pr_k', 3), keep_sets=sets)
+                             pr_k=getattr(args, 'pr_k', 3), keep_sets=sets, hist_range=getattr(args, 'hist_range', None),
+                             hist_levels=getattr(args, 'hist_levels', 1), keep_hists=hists)
             if metric_tap is not None:
                 metric_tap.append((phase, tag + suffix, m, kept))
             if metric_sets is not None:
                 metric_sets.extend((phase, tag + suffix, n, D) for n, D in sets)
+            if metric_hists is not None:
+                metric_hists.append((phase, tag + suffix, hists))
             return m
 
         g_lr0, d_lr0 = scale_lr(args.g_lr, args.d_lr, args.g_scaling, args.d_scaling, horovod, global_size)
