@@ -1308,7 +1308,9 @@ def _upconv_dgrad(g, w, coef, flip):
             if gx is not None:
                 return gx
         cin, cout = (w.shape[4], w.shape[3]) if flip else (w.shape[3], w.shape[4])
-        mode = min(_pool_mode(g, w.shape[:3], cin, cout), 2)      # (3: this caller keeps the D x W means + the H pairs)
+        mode = _pool_mode(g, w.shape[:3], cin, cout)
+        if mode == 3:      # this caller needs the SUM: it keeps the D x W means + the H pairs (min(mode, 2) asked for the H x W
+            mode = 1       # means instead, which a 32 -> 32 layer has no kernel for: the full-resolution gradient was written)
         if mode:
             res = raw_conv(g, w, coef, flip, False, pool=mode)
             if res is not None:      # means over four voxels; the remaining pairs and the factor back to a sum follow

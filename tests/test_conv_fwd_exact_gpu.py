@@ -33,6 +33,7 @@ import pytest
 import torch
 
 from tests import fwdref as R
+from tests import gref as G
 from tests import wgref as W
 
 pytestmark = pytest.mark.gpu
@@ -507,11 +508,7 @@ def test_route_is_exact(c, sg_env):
 
 
 # ----------------------------------------------------------------------------------------------------------------------
-# pixel_norm: y = v * rsqrt(mean_c(v^2) + eps) on the exact f32 accumulator values v.  The f32 error, counted from the epilogues
-# (conv3d.hip:205-224 and its copies): the sum of C exact squares by FMA, at most C roundings of a positive sum (C 2^-24 relative),
-# the product with the rounded 1 / C (2), the eps add (1), halved by the square root; rsqrtf within 2 ulp (4 2^-24); the product
-# with v (1): (C / 2 + 1.5 + 4 + 1) 2^-24 |y|.  f32 outputs get that term alone, bf16 outputs half a bf16 ulp (of |ref| + that
-# term) on top.  pn_scale gets the scale's share (C / 2 + 5.5) 2^-24.
+# pixel_norm: inside the bound tests/gref.py derives above pn_check (shared with tests/test_autograd_gen_exact_gpu.py).
 # ----------------------------------------------------------------------------------------------------------------------
 PN = [
     Case('pn_3w', 'conv_fwd3w<bf16,32->32>', 2, 32, 32, (5, 20, 64), bias=True, act=True, sign=True, pn=True),
@@ -539,17 +536,7 @@ PN = [
 ]
 
 
-def _pn_check(cid, y, scale, pre, dt, cout):
-    ref, s = R.pixel_norm(pre, 1e-8)
-    f32_term = (cout / 2 + 6.5) * 2.0 ** -24 * ref.abs()
-    bound = f32_term if dt == F32 else f32_term + 0.5 * R.bf16_ulp(ref.abs() + f32_term)
-    err = (y.double() - ref).abs()
-    worst = float((err / bound.clamp_min(1e-300)).max())
-    assert bool((err <= bound).all()), f'{cid}: y leaves the derived bound by a factor {worst}'
-    if scale is not None:
-        n, _, d, h, w = ref.shape
-        es = (scale.double().reshape(n, 1, d, h, w) - s).abs() / s
-        assert float(es.max()) <= (cout / 2 + 5.5) * 2.0 ** -24, f'{cid}: pn_scale'
+_pn_check = G.pn_check
 
 
 @pytest.mark.parametrize('c', PN, ids=[c.id for c in PN])
@@ -584,8 +571,7 @@ def test_rgb_head_on_the_stored_pixel_normed_output():
     _pn_check(c.id, y, scale, d['pre'], BF, 32)
     _assert_equal(c.id, signs, R.sign_words(d['pre']), 'sign words')
     ref = R.rgb_head(y, rgb_w, 2.0)
-    f32_term = 11 * 2.0 ** -24 * ((y.double().abs() * rgb_w.double().abs().reshape(1, -1, 1, 1, 1)).sum(1, keepdim=True) + 2.0)
-    bound = f32_term + 0.5 * R.bf16_ulp(ref.abs() + f32_term)
+    bound = G.rgb_bound(y, rgb_w, 2.0, ref)
     err = (rgb.double() - ref).abs()
     assert bool((err <= bound).all())
 
