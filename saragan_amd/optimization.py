@@ -19,6 +19,7 @@ import numpy as np
 import torch
 
 from . import functional as F
+from . import step_capture as SC
 from .networks.loss import forward_discriminator, forward_generator, forward_simultaneous, linear_generator_link
 from .networks.ops import Op, ScalarVariable
 from .networks.pgan.variables import pgan_variable_shapes
@@ -375,6 +376,10 @@ class StepGraph:
         self._cond = None      # the label rows of the step in flight (a conditional graph; run() sets them)
         on, max_consecutive = nonfinite_guard_settings()
         self.guard = NonFiniteGuard(max_consecutive) if on else None
+        self._stepped, self._wanted = False, set()      # configure_guard: only before the first step; (key, net) of the step's fetches
+        self._captures = {}    # capture key -> dict: eager, ratios, probes, decided, used and, once captured, graph (a CapturedStep)
+        self._cap_clock, self._cap_pool = 0, None      # `used` of the entry touched last; the memory pool the captures share
+        self._issue_log = None  # tests: a list here records the issue order of replayed segments and bucket collectives
 
     def add_train(self, net, optimizer, names, clipping):
         self.trains.append(dict(net=net, optimizer=optimizer, names=names, clipping=bool(clipping)))
@@ -419,7 +424,7 @@ class StepGraph:
     # -- non-finite step guard ------------------------------------------------------------------------------------------
     def configure_guard(self, on=True, max_consecutive=None):
         """Turns the non-finite step guard on (or off) for this step graph, before its first step."""
-        if self.__dict__.get('_stepped'):
+        if self._stepped:
             raise RuntimeError('configure_guard: call it before the first training step of the step graph')
         self.guard = NonFiniteGuard(max_consecutive) if on else None
         self._refuse_guard_with_adasum()
@@ -511,7 +516,6 @@ class StepGraph:
         want_train = {f.net for f in fetches if f.key == 'train'}
         self._wanted = {(f.key, f.net) for f in fetches}
         real = feed
-        out = {}
         if all(f.key == 'gen_sample' for f in fetches):
             # sess.run(gen_sample) (metrics/save_metrics.py:104: fake images for the validation metrics): TF prunes the graph
             # to the generator; so does this -- fresh latents, the current weights and alpha, no discriminator pass
@@ -536,19 +540,12 @@ class StepGraph:
             alpha = float(c['alpha'].eval()) if isinstance(c['alpha'], ScalarVariable) else float(c['alpha'])
             net_args = (c['latent_dim'], alpha, c['phase'], c['base_shape'], c['kernel_spec'], c['filter_spec'],
                         c['activation'], c['leakiness'], c['loss_fn'])
-            if c['optim_strategy'] == 'simultaneous':
-                if self._capturable(train_ids, real):
-                    out = self._replay_or_capture(real, train_ids, want_train, net_args, alpha)
-                else:
-                    pend = self._compute_simultaneous(real, train_ids, net_args, out)
-                    for tid, info in pend:
-                        self._finish(tid, info, out, apply=tid in want_train)
-            else:                               # alternate: D step, then G forward on the updated D
-                no_dist = all(self.trains[t]['optimizer'].distributed is None for t in train_ids)
-                if no_dist and self._capturable(train_ids, real):
-                    out = self._replay_or_capture(real, train_ids, want_train, net_args, alpha, strategy='alternate')
-                else:
-                    self._compute_alternate(real, train_ids, want_train, net_args, out)
+            strategy = c['optim_strategy']      # alternate: D step, then G forward on the updated D (captured without a reducer only)
+            no_dist = strategy == 'simultaneous' or all(self.trains[t]['optimizer'].distributed is None for t in train_ids)
+            if no_dist and SC.capturable(self, train_ids, real):
+                out = self._replay_or_capture(real, train_ids, want_train, net_args, alpha, strategy)
+            else:
+                out = self._eager_step(real, train_ids, want_train, net_args, strategy)
         static = out.pop('__static__', False)     # a replayed graph's outputs live in buffers the next replay overwrites
         self.last = None if static else out
 
@@ -610,277 +607,38 @@ class StepGraph:
                 between(j)
         return pend
 
-    # -- hipGraph capture of the step -----------------------------------------------------------------------------
-    # The small phases and the 2-D configuration are HOST-bound: ~600-1500 kernel launches per step through Python,
-    # autograd and ctypes (config 1: 2.6 ms of wall time for 1.2 ms of kernels).  The whole step -- forward, both backward
-    # passes with the gradient penalty's double backward, the global-norm clip, the optimiser + EMA launches -- is captured
-    # ONCE into a hipGraph (torch.cuda.graph: the C-ABI launches go to torch's current stream, which is the capturing one;
-    # workspaces come from the graphs' shared private pool) and replayed as a single launch.  What varies per step is on
-    # the device or outside the captured region:
-    #   * the batch, the label rows of a conditional graph, the latents and the penalty's mixing weights live in fixed buffers
-    #     refilled before each replay (loss.StaticRandom), the instance noise reads its Philox offset from a device counter;
-    #   * the fade-in weights [alpha, 1 - alpha] (networks/ops.py:4-23: alpha moves EVERY step of a mixing phase) and each
-    #     optimiser's step size (lr schedule optimization.py:227-296; Adam's bias correction) are host arithmetic written to
-    #     a pinned mirror and sent with one small copy before the replay (functional.DevScalars; sg_axpby_dev,
-    #     sg_adam_ema_dev): a mixing phase replays ONE graph;
-    #   * with a gradient reducer attached (parallel.DistributedOptimizer) the captured region ends after the backward
-    #     passes; the bucket collectives and the optimiser launches follow eagerly (RCCL stays outside the graph).
-    # The graph is keyed by what is baked in (train ops, whether gradient norms are asked for, alpha's class {0, 1, in
-    # between}, batch shape, the label width L, dtype) -- NOT by the loss / sample fetches: every capture produces all of them -- and captured
-    # after three eager steps of the same key (every lazy one-time call has happened).
-    # SARAGAN_HIPGRAPH=1 forces capture, =0 forbids it; unset, a key is captured when its eager steps turn out host-bound
-    # (host enqueue time >= 0.8 x the device span of the step, measured on eager steps 2 and 3 of the key).
+    # -- hipGraph capture of the step (step_capture.py: when a key is captured, and what a captured key owns and does) --------
     _MAX_CAPTURES = 4
 
-    def _capturable(self, train_ids, real):
-        mode = os.environ.get('SARAGAN_HIPGRAPH', '')
-        if mode == '0' or not real.is_cuda:
-            return False
-        nets = {self.trains[t]['net'] for t in train_ids}
-        if not nets >= {'generator', 'discriminator'}:
-            return False                         # the full training step only
-        if any(type(self.trains[t]['optimizer'].distributed).__name__ == 'AdasumReducer' for t in train_ids):
-            return False                         # Adasum combines weight deltas around the optimiser step: eager
-        if F._lib.load().sg_prof_enabled():
-            return False                         # the profiler brackets launches with events: never inside a capture
-        from .networks import loss as L
-        return L.graph_safe(L._rng(real.device))
-
-    @staticmethod
-    def assert_no_live_accumulate_grad(params):
-        """Raises if any parameter's AccumulateGrad node is kept alive by an autograd graph somebody still holds.  Such a node
-        remembers the stream it was created on; reused inside a capture it runs on the non-capturing stream and
-        hipStreamEndCapture aborts the process (round 3: gpurun_out/hg.log).  A leaf's node is only weakly held by the tensor:
-        pass 1 marks every node it is handed and lets go of it; a node that pass 2 receives WITH the mark survived without
-        our reference, i.e. a live graph owns it."""
-        token = object()
-        edge = torch.autograd.graph.get_gradient_edge
-        for p in params:
-            if p.requires_grad and p.grad_fn is None:
-                edge(p).node.metadata['sg_capture_probe'] = token
-        held = [i for i, p in enumerate(params)
-                if p.requires_grad and p.grad_fn is None and edge(p).node.metadata.get('sg_capture_probe') is token]
-        if held:
-            raise RuntimeError(f'{len(held)} parameter(s) still have an AccumulateGrad node owned by a live autograd graph '
-                               f'(first: #{held[0]}): drop the previous step\'s outputs before a step is captured')
-
-    def _replay_or_capture(self, real, train_ids, want_train, net_args, alpha, strategy='simultaneous'):
-        from .networks import loss as L
-        alpha_class = 'mix' if 0.0 < alpha < 1.0 else float(alpha)
-        norms = tuple(sorted(t for t in train_ids if ('max_norm', t) in self._wanted))
-        dist_ids = tuple(t for t in train_ids if self.trains[t]['optimizer'].distributed is not None)
-        key = (tuple(train_ids), tuple(sorted(want_train)), norms, alpha_class, tuple(real.shape), str(compute_dtype()), strategy,
-               self.guard is not None,
-               strategy == 'simultaneous' and 'discriminator/' in self.store.rewritten,      # (a pending refresh is baked in)
-               None if self._cond is None else int(self._cond.shape[1]))
-        caps = self.__dict__.setdefault('_captures', {})
-        ent = caps.get(key)
-        if ent is None:
-            ent = caps[key] = dict(eager=0, ratios=[])
-        ent['used'] = self.__dict__['_cap_clock'] = self.__dict__.get('_cap_clock', 0) + 1
-        base = L._rng(real.device)
-        forced = os.environ.get('SARAGAN_HIPGRAPH', '') == '1'
-
-        def eager():
-            out = {}
-            if strategy == 'alternate':
-                self._compute_alternate(real, train_ids, want_train, net_args, out)
-                return out
-            pend = self._compute_simultaneous(real, train_ids, net_args, out)
-            for tid, info in pend:
-                self._finish(tid, info, out, apply=tid in want_train)
-            return out
-
-        if 'graph' not in ent:
-            if ent.get('decided') == 'eager':
-                return eager()
-            if ent['eager'] < (2 if forced else 3):          # warm-up: the ordinary path, timed from its second step on
-                ent['eager'] += 1
-                if ent['eager'] == 1 or forced:
-                    return eager()
-                import time
-                e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
-                e0.record()
-                t0 = time.perf_counter()
-                out = eager()
-                host_ms = (time.perf_counter() - t0) * 1e3
-                e1.record()
-                ent.setdefault('probes', []).append((host_ms, e0, e1))
-                return out
-            if not forced:
-                for host_ms, e0, e1 in ent.pop('probes', []):
-                    e1.synchronize()
-                    ent['ratios'].append(host_ms / max(1e-6, e0.elapsed_time(e1)))
-                worst = min(ent['ratios']) if ent['ratios'] else 0.0
-                if dist_ids and torch.distributed.is_initialized() and torch.distributed.get_world_size() > 1:
-                    # every rank must take the SAME path: the eager step launches its buckets from autograd hooks as they become
-                    # ready, the captured one launches them in order after the replay -- ranks that disagree would issue their
-                    # collectives in different orders.  The decision is the minimum over ranks (all ranks reach this point at the
-                    # same step of the same key).
-                    t = torch.tensor([worst], device=real.device, dtype=torch.float64)
-                    torch.distributed.all_reduce(t, op=torch.distributed.ReduceOp.MIN)
-                    worst = float(t.item())
-                if worst < 0.8:      # the device is the bottleneck: nothing to gain
-                    ent['decided'] = 'eager'
-                    return eager()
-            # ---- capture
-            while sum('graph' in e for e in caps.values()) >= self._MAX_CAPTURES:      # bounded: oldest captured key goes
-                old = min((k for k, e in caps.items() if 'graph' in e), key=lambda k: caps[k]['used'])
-                del caps[old]
-            ent['real'] = real.clone()
-            fed_cond = self._cond
-            ent['cond'] = None if fed_cond is None else fed_cond.clone()      # the captured launches read the labels from here
-            self._cond = ent['cond']
-            ent['rnd'] = L.StaticRandom(base, real.shape[0], self.cfg['latent_dim'], real.device,
-                                        pattern=('z', 'g', 'z') if strategy == 'alternate' else ('z', 'g'))
-            ent['rnd'].draw()
-            ent['rnd'].sync_counter()
-            sc = ent['scalars'] = F.DevScalars(real.device, 8)
-            args = list(net_args)
-            if alpha_class == 'mix':
-                args[1] = sc.coef(0, alpha)
-                sc.set(1, 1.0 - alpha)
-            ent['opt'] = []                                   # (train id, optimiser, scalar slot) of the captured applies
-            ent['glr'] = []                                   # guard: (train id, optimiser) whose base lr the host writes
-            lr_dev = {}
-            if not dist_ids:
-                for i, tid in enumerate(t for t in train_ids if t in want_train):
-                    o = self.trains[tid]['optimizer']
-                    if self.guard is not None:      # the step count and the step size are the device's (sg_guard_step)
-                        lr_dev[tid] = self.guard.lr_coef(tid, o.lr_value())
-                        ent['glr'].append((tid, o))
-                    else:
-                        lr_dev[tid] = sc.coef(2 + i, o.next_step_size())
-                        ent['opt'].append((tid, o, 2 + i))
-            sc.flush()
-            if ent['glr']:
-                self.guard.lr.flush()
-            ent['out'] = {}
-            g = torch.cuda.CUDAGraph()
-            L.set_random_source(ent['rnd'])
-            ent['rnd'].counting = True
-            # No live autograd graph may own the parameters' AccumulateGrad nodes when the capture begins (see
-            # assert_no_live_accumulate_grad): the last step's outputs are dropped first, then the invariant is CHECKED.
-            self.last = None
-            # every weight image the step uses is (re)written INSIDE the graph, from the weights of the day: the images of the
-            # eager warm-up steps stay where they are and the first convolution of the graph refreshes them all in one launch
-            F.mark_packs_stale()
-            marks = []
-            try:
-                self.assert_no_live_accumulate_grad(self.store.grad_leaves('generator/') +
-                                                    self.store.grad_leaves('discriminator/'))
-                torch.cuda.synchronize()
-                pool = self.__dict__.get('_cap_pool')
-                if pool is None:
-                    pool = self.__dict__['_cap_pool'] = torch.cuda.graph_pool_handle()
-                if strategy == 'alternate':      # (no reducer attached: run() checked) the two half-steps in one graph: the second one's
-                    with torch.cuda.graph(g, pool=pool):      # first convolution refreshes the weight images from the updated D
-                        self._compute_alternate(ent['real'], train_ids, want_train, tuple(args), ent['out'], lr_dev=lr_dev, marks=marks)
-                    ent['pend'] = []
-                elif not dist_ids:
-                    with torch.cuda.graph(g, pool=pool):
-                        ent['pend'] = self._compute_simultaneous(ent['real'], train_ids, tuple(args), ent['out'], arm_dist=False)
-                        for tid, info in ent['pend']:
-                            self._finish(tid, info, ent['out'], apply=tid in want_train, lr_dev=lr_dev.get(tid), marks=marks)
-                else:
-                    # With a gradient reducer attached the step is captured as SEGMENTS that end where a network's gradients are
-                    # complete: [forward + first backward pass] [second backward pass].  A replay launches the first network's
-                    # bucket collectives (RCCL's stream) behind segment 0 and replays segment 1 while they run: the all-reduce
-                    # of one network overlaps with the backward pass of the other, as in the eager step (round 4 replayed ONE
-                    # graph and launched every bucket behind it: nothing overlapped, VERDICT r4 "missing" 1a).  The segments
-                    # are captured on one stream (autograd runs a backward node on the stream of its forward: a second capture
-                    # on another stream would find the first one's nodes on a non-capturing stream) and share the memory pool.
-                    cap_stream = torch.cuda.Stream()
-                    segs, cm = [g], {}
-
-                    def cut(j):
-                        cm['cur'].__exit__(None, None, None)
-                        nxt = torch.cuda.CUDAGraph()
-                        segs.append(nxt)
-                        cm['cur'] = torch.cuda.graph(nxt, pool=pool, stream=cap_stream)
-                        cm['cur'].__enter__()
-                    cm['cur'] = torch.cuda.graph(g, pool=pool, stream=cap_stream)
-                    cm['cur'].__enter__()
-                    try:
-                        ent['pend'] = self._compute_simultaneous(ent['real'], train_ids, tuple(args), ent['out'], arm_dist=False,
-                                                                 between=cut)
-                    except BaseException as exc:
-                        cm['cur'].__exit__(type(exc), exc, exc.__traceback__)
-                        raise
-                    else:
-                        cm['cur'].__exit__(None, None, None)
-                    ent['segments'] = segs
-            except BaseException:
-                # nothing was applied: the optimisers' step counts go back, and this key stays on the eager path from now on
-                # (the error itself is the caller's to see: a capture that failed half-way is not retried silently)
-                for _, o, _ in ent['opt']:
-                    o.t -= 1
-                ent['decided'] = 'eager'
-                for k_ in ('real', 'cond', 'rnd', 'scalars', 'opt', 'glr', 'out', 'pend'):
-                    ent.pop(k_, None)
-                # a kept filter-gradient workspace first made inside the failed capture had its zero-fill only RECORDED: it
-                # (and any other) goes, the next eager step makes clean ones
-                F.clear_kept_workspaces()
-                raise
-            finally:
-                self._cond = fed_cond
-                L.set_random_source(base)
-                F.mark_packs_stale()      # (a capture records launches without running them)
-            ent['rnd'].counting = False
-            ent['rewritten'] = set(self.store.rewritten)      # (what a step of this kind leaves pending: repeated by a replay)
-            ent['packs'] = F.live_packs()      # the graph reads (and refreshes) these images: they live as long as it does
-            ent['marks'] = marks
-            # replays need the captured launches and the output buffers, not the Python autograd graph: without it the
-            # AccumulateGrad nodes made on the capturing stream go away too (a later eager step would find them on the
-            # wrong stream and synchronise)
-            ent['out'] = {k: (v.detach() if torch.is_tensor(v) else v) for k, v in ent['out'].items()}
-            ent['graph'] = g
+    def _eager_step(self, real, train_ids, want_train, net_args, strategy):
+        out = {}
+        if strategy == 'alternate':
+            self._compute_alternate(real, train_ids, want_train, net_args, out)
         else:
-            ent['real'].copy_(real, non_blocking=True)
-            if ent['cond'] is not None:
-                ent['cond'].copy_(self._cond, non_blocking=True)
-            ent['rnd'].draw()
-            ent['rnd'].sync_counter()
-            sc = ent['scalars']
-            if alpha_class == 'mix':
-                sc.set(0, alpha)
-                sc.set(1, 1.0 - alpha)
-            for tid, o, slot in ent['opt']:
-                sc.set(slot, o.next_step_size())
-            if alpha_class == 'mix' or ent['opt']:
-                sc.flush()
-            if ent['glr']:
-                for tid, o in ent['glr']:
-                    self.guard.lr.set(tid, o.lr_value())
-                self.guard.lr.flush()
-        log = self.__dict__.get('_issue_log')          # tests: the host-side issue order of segments and bucket collectives
-        if dist_ids and 'segments' in ent:
-            # segment k, then the collectives of the network whose gradients it completed, then segment k + 1 (which they overlap)
-            for k, (seg, (tid, info)) in enumerate(zip(ent['segments'], ent['pend'])):
-                seg.replay()
-                if log is not None:
-                    log.append(('segment', k))
-                if info['dist'] is not None:
-                    info['dist'].begin(info['flat']['grad'], info['ranges'], [self.store.stand_in(n) for n in info['names']], None)
-                    nb = info['dist'].launch_all()
-                    if log is not None:
-                        log.append(('buckets', k, tid, nb))
-        else:
-            ent['graph'].replay()
-        F.mark_packs_stale()                   # (the graph's optimiser launches rewrote the parameters)
-        self.store.rewritten = set(ent['rewritten'])
-        ent['rnd'].after_replay()
-        out = dict(ent['out'])
-        out['__static__'] = True
-        if dist_ids:       # the waits and the optimiser launches follow eagerly
-            for tid, info in ent['pend']:
-                if info['dist'] is not None and 'segments' not in ent:
-                    info['dist'].begin(info['flat']['grad'], info['ranges'], [self.store.stand_in(n) for n in info['names']], None)
+            for tid, info in self._compute_simultaneous(real, train_ids, net_args, out):
                 self._finish(tid, info, out, apply=tid in want_train)
-        elif self.ema is not None:
-            for prefix, ranges in ent['marks']:
-                self.ema.mark_updated(prefix, ranges)
         return out
+
+    def _replay_or_capture(self, real, train_ids, want_train, net_args, alpha, strategy):
+        key = SC.capture_key(self, real, train_ids, want_train, alpha, strategy)
+        ent = self._captures.get(key)
+        if ent is None:
+            ent = self._captures[key] = dict(eager=0, ratios=[])
+        ent['used'] = self._cap_clock = self._cap_clock + 1
+        if 'graph' in ent:
+            ent['graph'].refill(real, self._cond, alpha)
+        else:
+            dist_ids = tuple(t for t in train_ids if self.trains[t]['optimizer'].distributed is not None)
+            out = SC.warm_up(ent, lambda: self._eager_step(real, train_ids, want_train, net_args, strategy), bool(dist_ids), real.device)
+            if out is not None:
+                return out
+            SC.evict(self._captures, self._MAX_CAPTURES)
+            try:
+                ent['graph'] = SC.CapturedStep(self, real, train_ids, want_train, net_args, alpha, strategy, dist_ids)
+            except BaseException:      # this key stays on the eager path from now on
+                ent['decided'] = 'eager'
+                raise
+        return ent['graph'].replay()
 
     def _backward(self, tid, out, retain=False, arm_dist=True):
         tr = self.trains[tid]
@@ -994,12 +752,7 @@ class StepGraph:
         elif apply:
             ema_flat = self.ema.shadow_flat(info['prefix']) if self.ema is not None else None
             ema_decay = self.ema.decay if self.ema is not None else 0.0
-            if guard is not None:
-                tr['optimizer'].apply(info['prefix'], flat, ranges, gscale, ema_flat, ema_decay, guard=guard)
-            elif lr_dev is not None:
-                tr['optimizer'].apply(info['prefix'], flat, ranges, gscale, ema_flat, ema_decay, lr_dev=lr_dev)
-            else:
-                tr['optimizer'].apply(info['prefix'], flat, ranges, gscale, ema_flat, ema_decay)
+            tr['optimizer'].apply(info['prefix'], flat, ranges, gscale, ema_flat, ema_decay, lr_dev=lr_dev, guard=guard)
             self.store.mark_rewritten(info['prefix'])
             if self.ema is not None:
                 self.ema.mark_updated(info['prefix'], ranges)

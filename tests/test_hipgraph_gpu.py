@@ -17,7 +17,8 @@ pytestmark = pytest.mark.gpu
 NAME = 'oracle_step_p3_wgan_a000.npz'
 
 
-def _run(golden_dir, steps, dtype, captured, mixing=False, clipping=False, keep=False, reload_at=None, run_ahead=False, alpha_step=0.11, strategy='simultaneous'):
+def _run(golden_dir, steps, dtype, captured, mixing=False, clipping=False, keep=False, reload_at=None, run_ahead=False, alpha_step=0.11, strategy='simultaneous',
+         norm_steps=(), watch=None):
     import saragan_amd.optimization as opt
     from saragan_amd.ExtendedEMA import ExtendedEMA
     from saragan_amd.networks import loss as L
@@ -66,7 +67,9 @@ def _run(golden_dir, steps, dtype, captured, mixing=False, clipping=False, keep=
             real = reals[i]
             if i == reload_at:      # the weights change under the graph (a checkpoint restored mid-run): torch copies, new versions
                 store.load_state_dict({k: v * 0.5 for k, v in fx['p0'].items()}, strict=True)
-            res = sess.run(fetch, feed_dict={ph: real})
+            res = sess.run(fetch + ([tup[10], tup[11]] if i in norm_steps else []), feed_dict={ph: real})
+            if watch is not None:
+                watch(i, tup[0].graph)
             gl, dl = res[2], res[3]
             sess.run(ema_op)
             if keep:
@@ -192,16 +195,44 @@ def test_host_bound_step_is_captured_without_a_switch(golden_dir):
     assert not [k for k in w0 if not torch.equal(w0[k], w1[k])]
 
 
+def test_the_oldest_capture_is_evicted_whole_and_its_key_captured_again(golden_dir, monkeypatch):
+    """At most _MAX_CAPTURES keys hold a graph (here: 1).  Key A fetches the train ops and the losses, key B the two max-norm handles
+    as well (the key's `norms` differ; clipping stays off).  Three steps of A (two eager warm-up steps, capture), three of B -- its
+    capture deletes A's entry --, three of A, which warms up and is captured again in B's place.  Weights, EMA shadows and losses
+    equal those of the same nine eager steps bit for bit."""
+    import saragan_amd
+    import saragan_amd.optimization as opt
+    monkeypatch.setattr(opt.StepGraph, '_MAX_CAPTURES', 1)
+    seen = {}
+
+    def watch(i, graph):
+        if i in (5, 8):      # (does the key fetch norms, does its entry hold a graph) after groups 2 and 3
+            seen[i] = [(k[2] != (), 'graph' in e) for k, e in graph._captures.items()]
+    saragan_amd.set_deterministic(True)
+    try:
+        w0, l0, n0 = _run(golden_dir, 9, torch.float32, captured=False, norm_steps=(3, 4, 5))
+        w1, l1, n1 = _run(golden_dir, 9, torch.float32, captured=True, norm_steps=(3, 4, 5), watch=watch)
+    finally:
+        saragan_amd.set_deterministic(False)
+    assert n0 == 0 and n1 == 1, (n0, n1)
+    assert seen[5] == [(True, True)], seen               # B's entry holds the only graph; A's entry is gone
+    assert [norms for norms, cap in seen[8] if cap] == [False], seen      # and after group 3 the only graph is A's
+    assert [len(v) for v in l0] == [2, 2, 2, 4, 4, 4, 2, 2, 2]
+    assert l0 == l1, (l0, l1)
+    bad = [k for k in w0 if not torch.equal(w0[k], w1[k])]
+    assert not bad, bad
+
+
 def test_capture_refuses_a_live_autograd_graph():
     """the invariant behind round 3's hipStreamEndCapture crash is checked, not assumed (CPU-visible state)."""
-    import saragan_amd.optimization as opt
+    from saragan_amd import step_capture
     ps = [torch.nn.Parameter(torch.randn(4, device='cuda')) for _ in range(3)]
-    opt.StepGraph.assert_no_live_accumulate_grad(ps)
+    step_capture.assert_no_live_accumulate_grad(ps)
     y = (ps[2] * 2).sum()
     with pytest.raises(RuntimeError, match='AccumulateGrad'):
-        opt.StepGraph.assert_no_live_accumulate_grad(ps)
+        step_capture.assert_no_live_accumulate_grad(ps)
     del y
-    opt.StepGraph.assert_no_live_accumulate_grad(ps)
+    step_capture.assert_no_live_accumulate_grad(ps)
 
 
 def test_a_capture_that_cannot_start_raises_and_leaves_the_run_usable(golden_dir, monkeypatch):
