@@ -590,8 +590,12 @@ int sg_augment_affine_apply(const void* x, void* y, const float* params, int32_t
                             float fill, uint32_t flags, sg_dtype dt, sg_stream_t st);
 
 /* ---- validation metrics on device tensors (metrics/swd.py:13-123, metrics/skim_metrics.py:8-45) ---------------- */
-/* One axis of a separable FIR filter over x viewed as [outer, n, inner] (f32, or f64 when `f64` != 0; accumulated in
- * f64 either way): y = alpha * value + add (add may be NULL; it is shaped like y).
+/* One axis of a separable FIR filter over x viewed as [outer, n, inner], accumulated in f64: y = alpha * value + add (add
+ * may be NULL; it is shaped and typed like y; alpha * value is rounded to y's type before the addition, as a caller that
+ * stores the filtered value and then adds would have it).  `f64` names the types of x and y: 0 f32 -> f32, 1 f64 -> f64,
+ * 2 f32 -> f64, 3 f64 -> f32 (any other value: SG_EINVAL).  The pyramid runs its three passes as 2, 1, 3: the f64
+ * intermediates are exact for f32 volumes of moderate range, so a step rounds once, like the reference's one 5x5x5
+ * convolution (which scipy accumulates in f64).
  *   mode 0: value[o] = sum_t taps[t] x[B(o + t - r)]                    extent n      (scipy.ndimage.gaussian_filter1d)
  *   mode 1: value[o] = sum_t taps[t] x[B(2o + t - r)]                   extent (n+1)/2  (pyr_down, swd.py:63-66:
  *           the 5x5x5 binomial filter is separable, then [::2])
@@ -602,8 +606,12 @@ int sg_filter_axis(const void* x, void* y, const void* add, int64_t outer, int32
 /* get_descriptors_for_minibatch (swd.py:13-26): x f32 [n_img, c, d, h, w] (NCDHW, as the metrics receive it);
  * out[nh, c, i, j, k] = x[nh / per_image, c, d0[nh] + i - rd, h0[nh] + k - rw, w0[nh] + j - rh], out shaped
  * [n_img * per_image, c, 2rd+1, 2rh+1, 2rw+1] -- the reference adds its fourth-axis offsets to the W centre and its
- * fifth-axis offsets to the H centre, and so does this.  d0 / h0 / w0: DEVICE int32[n_img * per_image], centres the
- * caller drew inside [r, extent - r). */
+ * fifth-axis offsets to the H centre, and so does this.  d0 / h0 / w0: DEVICE int32[n_img * per_image].
+ * PRECONDITION on the centres, with the offsets each one really carries: d0 in [rd, d - rd), h0 in [rw, h - rw), w0 in
+ * [rh, w - rh).  The library cannot see device-side centres: it only refuses (SG_EINVAL, before any launch) a NULL pointer,
+ * n_img, c or per_image < 1, a negative radius, and extents with no legal centre at all (d < 2rd+1, h < 2rw+1, w < 2rh+1);
+ * a centre outside its range reads outside x.  The reference draws the W centre from [rw, w - rw) and the H centre from
+ * [rh, h - rh): with rh != rw the caller has to check its draws on the host (saragan_amd/metrics/swd.py raises ValueError). */
 int sg_swd_gather(const float* x, float* out, const int32_t* d0, const int32_t* h0, const int32_t* w0, int32_t n_img,
                   int32_t c, int32_t d, int32_t h, int32_t w, int32_t per_image, int32_t rd, int32_t rh, int32_t rw,
                   sg_stream_t st);

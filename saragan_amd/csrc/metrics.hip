@@ -36,19 +36,22 @@ __device__ __forceinline__ int sg_border(int i, int n, int border) {
   return i >= n ? period - 1 - i : i;
 }
 
-template <typename T>
+// TI: the type of x, TO: the type of y and add.  The pyramid keeps the intermediates of its three separable passes in f64
+// (f32 -> f64, f64 -> f64, f64 -> f32), where they are exact for f32 data of moderate range: the result is then rounded to
+// f32 once, as the reference's single 5x5x5 convolution in f64 is.
+template <typename TI, typename TO>
 __global__ __launch_bounds__(256) void filter_axis_kernel(FilterArgs a) {
   const int64_t total = a.outer * a.n_out * a.inner;
-  const T* x = reinterpret_cast<const T*>(a.x);
-  const T* add = reinterpret_cast<const T*>(a.add);
-  T* y = reinterpret_cast<T*>(a.y);
+  const TI* x = reinterpret_cast<const TI*>(a.x);
+  const TO* add = reinterpret_cast<const TO*>(a.add);
+  TO* y = reinterpret_cast<TO*>(a.y);
   const int r = a.ntaps >> 1;
   for (int64_t e = (int64_t)blockIdx.x * 256 + threadIdx.x; e < total; e += (int64_t)gridDim.x * 256) {
     const int64_t in_ = e % a.inner;
     const int64_t q = e / a.inner;
     const int o = (int)(q % a.n_out);
     const int64_t ou = q / a.n_out;
-    const T* line = x + ou * a.n * a.inner + in_;
+    const TI* line = x + ou * a.n * a.inner + in_;
     double acc = 0.0;
     if (a.mode == 2) {            // zero insertion: z[2k] = x[k], z[odd] = 0, extent 2n
       for (int t = 0; t < a.ntaps; ++t) {
@@ -61,8 +64,10 @@ __global__ __launch_bounds__(256) void filter_axis_kernel(FilterArgs a) {
         acc += a.taps[t] * (double)line[(int64_t)sg_border(c + t - r, a.n, a.border) * a.inner];
     }
     acc *= a.alpha;
-    if (add != nullptr) acc += (double)add[e];
-    y[e] = (T)acc;
+    // the reference has the filtered value in the output type before it adds (level - pyr_up(..), swd.py:81): round first.
+    // (The f64 sum of two f32 values rounds to f32 exactly as their f32 sum does.)
+    if (add != nullptr) acc = (double)(TO)acc + (double)add[e];
+    y[e] = (TO)acc;
   }
 }
 
@@ -242,14 +247,15 @@ __global__ __launch_bounds__(256) void swd_rowdist_kernel(const float* __restric
   if (threadIdx.x == 0) out[1 + blockIdx.x] = S;
 }
 
-// out[0] = scale * sum(part[0 .. count))   (one block, fixed order)
+// out[0] = sum(part[0 .. count)) / divisor   (one block, fixed order; a division, as the means it restates are:
+// sum * (1 / divisor) rounds twice and is one ulp off np.mean for most divisors that are no power of two)
 __global__ __launch_bounds__(256) void sum_final_kernel(const double* __restrict__ part, double* __restrict__ out, int count,
-                                                        double scale) {
+                                                        double divisor) {
   __shared__ double sh[8];
   double s = 0.0;
   for (int i = threadIdx.x; i < count; i += 256) s += part[i];
   const double S = sg_block_sum(s, sh);
-  if (threadIdx.x == 0) out[0] = S * scale;
+  if (threadIdx.x == 0) out[0] = S / divisor;
 }
 
 __global__ __launch_bounds__(256) void sqdiff_partial_kernel(const double* __restrict__ a, const double* __restrict__ b,
@@ -347,15 +353,20 @@ int sg_filter_axis(const void* x, void* y, const void* add, int64_t outer, int32
                    int32_t ntaps, int32_t mode, int32_t border, double alpha, int32_t f64, sg_stream_t st) {
   if (x == nullptr || y == nullptr || taps == nullptr || x == y) return SG_EINVAL;
   if (outer < 1 || n < 1 || inner < 1 || ntaps < 1 || ntaps > MAX_TAPS || (ntaps & 1) == 0) return SG_EINVAL;
-  if (mode < 0 || mode > 2 || border < 0 || border > 1 || n > (1 << 28)) return SG_EINVAL;
+  if (mode < 0 || mode > 2 || border < 0 || border > 1 || n > (1 << 28) || f64 < 0 || f64 > 3) return SG_EINVAL;
   FilterArgs a;
   a.x = x; a.y = y; a.add = add; a.outer = outer; a.inner = inner; a.n = n;
   a.n_out = mode == 1 ? (n + 1) / 2 : (mode == 2 ? 2 * n : n);
   a.ntaps = ntaps; a.mode = mode; a.border = border; a.alpha = alpha;
   for (int t = 0; t < MAX_TAPS; ++t) a.taps[t] = t < ntaps ? taps[t] : 0.0;
   const int64_t total = outer * a.n_out * inner;
-  if (f64) hipLaunchKernelGGL(filter_axis_kernel<double>, dim3(grid_for(total, 256, 16384)), dim3(256), 0, sg_st(st), a);
-  else hipLaunchKernelGGL(filter_axis_kernel<float>, dim3(grid_for(total, 256, 16384)), dim3(256), 0, sg_st(st), a);
+  const dim3 grid(grid_for(total, 256, 16384));
+  switch (f64) {
+    case 0: hipLaunchKernelGGL((filter_axis_kernel<float, float>), grid, dim3(256), 0, sg_st(st), a); break;
+    case 1: hipLaunchKernelGGL((filter_axis_kernel<double, double>), grid, dim3(256), 0, sg_st(st), a); break;
+    case 2: hipLaunchKernelGGL((filter_axis_kernel<float, double>), grid, dim3(256), 0, sg_st(st), a); break;
+    default: hipLaunchKernelGGL((filter_axis_kernel<double, float>), grid, dim3(256), 0, sg_st(st), a); break;
+  }
   SG_LAUNCH_CHECK();
   return SG_OK;
 }
@@ -431,7 +442,7 @@ int sg_swd_distance(const float* pa, const float* pb, double* out, int32_t rows,
   if (pa == nullptr || pb == nullptr || out == nullptr || rows < 1 || n < 1 || npad < n) return SG_EINVAL;
   hipLaunchKernelGGL(swd_rowdist_kernel, dim3(rows), dim3(256), 0, sg_st(st), pa, pb, out, n, npad);
   SG_LAUNCH_CHECK();
-  hipLaunchKernelGGL(sum_final_kernel, dim3(1), dim3(256), 0, sg_st(st), out + 1, out, rows, 1.0 / ((double)rows * (double)n));
+  hipLaunchKernelGGL(sum_final_kernel, dim3(1), dim3(256), 0, sg_st(st), out + 1, out, rows, (double)rows * (double)n);
   SG_LAUNCH_CHECK();
   return SG_OK;
 }
@@ -446,7 +457,7 @@ int sg_sqdiff_mean(const double* a, const double* b, double* out, int64_t numel,
   const int blocks = grid_for(numel, 256 * 8, 1024);
   hipLaunchKernelGGL(sqdiff_partial_kernel, dim3(blocks), dim3(256), 0, sg_st(st), a, b, part, numel);
   SG_LAUNCH_CHECK();
-  hipLaunchKernelGGL(sum_final_kernel, dim3(1), dim3(256), 0, sg_st(st), part, out, blocks, 1.0 / (double)numel);
+  hipLaunchKernelGGL(sum_final_kernel, dim3(1), dim3(256), 0, sg_st(st), part, out, blocks, (double)numel);
   SG_LAUNCH_CHECK();
   return SG_OK;
 }
@@ -486,7 +497,7 @@ int sg_ssim_mean(const double* ux, const double* uy, const double* uxx, const do
                      crop, cov_norm, c1, c2);
   SG_LAUNCH_CHECK();
   const double count = (double)(s0 - 2 * crop0) * (double)(s1 - 2 * crop) * (double)(s2 - 2 * crop) * (double)c;
-  hipLaunchKernelGGL(sum_final_kernel, dim3(1), dim3(256), 0, sg_st(st), part, out, blocks, 1.0 / count);
+  hipLaunchKernelGGL(sum_final_kernel, dim3(1), dim3(256), 0, sg_st(st), part, out, blocks, count);
   SG_LAUNCH_CHECK();
   return SG_OK;
 }

@@ -1,6 +1,7 @@
 """SURFGAN_3D/metrics/swd.py:13-123 with the volumes resident on the GPU, on the library's own kernels
 (csrc/metrics.hip through the C ABI): the Laplacian pyramid as separable 5-tap passes with the decimation / zero insertion
-and the level subtraction fused (`sg_filter_axis`), neighbourhood descriptors by one gather (`sg_swd_gather`), channel
+and the level subtraction fused (`sg_filter_axis`; float64 between the passes of a step, so the levels equal the reference's
+bit for bit), neighbourhood descriptors by one gather (`sg_swd_gather`), channel
 normalisation (`sg_desc_normalize`), projections on the random directions (`sg_swd_project`), a bitonic sort per direction
 (`sg_sort_rows`) and the mean absolute difference (`sg_swd_distance`).  torch only holds the device buffers.  Random
 numbers (neighbourhood positions, projection directions) are drawn on the host from numpy's global generator in the
@@ -38,17 +39,25 @@ def _st():
     return C.c_void_p(torch.cuda.current_stream().cuda_stream)
 
 
-def _filter_axis(x, dim, mode, alpha=1.0, add=None):
-    """One axis of the separable binomial filter (mirror borders): decimating (`_DOWN`) or zero-inserting (`_UP`)."""
+_IO = {(torch.float32, torch.float32): 0, (torch.float64, torch.float64): 1, (torch.float32, torch.float64): 2,
+       (torch.float64, torch.float32): 3}
+
+
+def _filter_axis(x, dim, mode, alpha=1.0, add=None, out=torch.float64):
+    """One axis of the separable binomial filter (mirror borders): decimating (`_DOWN`) or zero-inserting (`_UP`).
+    The first two passes of a pyramid step write float64 (`out`), the third float32: the intermediates are then exact for
+    float32 volumes of moderate range and the step rounds once, as the reference's single 5x5x5 convolution does (which
+    scipy accumulates in float64).  With float32 intermediates the deeper Laplacian levels are one float32 ulp off."""
     shape = list(x.shape)
     n = shape[dim]
     outer = int(np.prod(shape[:dim], dtype=np.int64))
     inner = int(np.prod(shape[dim + 1:], dtype=np.int64))
     shape[dim] = (n + 1) // 2 if mode == _DOWN else 2 * n
-    y = torch.empty(shape, dtype=x.dtype, device=x.device)
+    y = torch.empty(shape, dtype=out, device=x.device)
     if add is not None:
-        assert add.shape == y.shape and add.is_contiguous() and add.dtype == x.dtype
-    _lib.check(_lib.load().sg_filter_axis(_p(x), _p(y), _p(add), outer, n, inner, _TAPS_C, 5, mode, _MIRROR, alpha, 0, _st()),
+        assert add.shape == y.shape and add.is_contiguous() and add.dtype == out
+    _lib.check(_lib.load().sg_filter_axis(_p(x), _p(y), _p(add), outer, n, inner, _TAPS_C, 5, mode, _MIRROR, alpha,
+                                         _IO[x.dtype, out], _st()),
                'sg_filter_axis')
     return y
 
@@ -57,9 +66,8 @@ def pyr_down(minibatch):
     """swd.py:63-66 (matches cv2.pyrDown per axis): the filter runs only where [::2] keeps a sample."""
     x = _dev(minibatch)
     assert x.dim() == 5
-    for d in (4, 3, 2):
-        x = _filter_axis(x, d, _DOWN)
-    return x
+    x = _filter_axis(_filter_axis(x, 4, _DOWN), 3, _DOWN)
+    return _filter_axis(x, 2, _DOWN, out=torch.float32)
 
 
 def pyr_up(minibatch, _level=None):
@@ -70,8 +78,8 @@ def pyr_up(minibatch, _level=None):
     x = _filter_axis(x, 2, _UP, 2.0)
     x = _filter_axis(x, 3, _UP, 2.0)
     if _level is None:
-        return _filter_axis(x, 4, _UP, 2.0)
-    return _filter_axis(x, 4, _UP, -2.0, add=_level)
+        return _filter_axis(x, 4, _UP, 2.0, out=torch.float32)
+    return _filter_axis(x, 4, _UP, -2.0, add=_level, out=torch.float32)
 
 
 def generate_laplacian_pyramid(minibatch, num_levels):
@@ -89,20 +97,27 @@ def reconstruct_laplacian_pyramid(pyramid):
     for level in pyramid[-2::-1]:
         x = _filter_axis(minibatch, 2, _UP, 2.0)
         x = _filter_axis(x, 3, _UP, 2.0)
-        minibatch = _filter_axis(x, 4, _UP, 2.0, add=_dev(level))
+        minibatch = _filter_axis(x, 4, _UP, 2.0, add=_dev(level), out=torch.float32)
     return minibatch
 
 
 def get_descriptors_for_minibatch(minibatch, nhood_size, nhoods_per_image):
     """swd.py:13-26: nhoods_per_image random (2D+1) x (2H+1) x (2W+1) neighbourhoods per volume."""
-    x = _dev(minibatch)
-    S = x.shape
+    S = tuple(minibatch.shape)
     assert len(S) == 5
     N = nhoods_per_image * S[0]
     D, H, W = nhood_size[0] // 2, nhood_size[1] // 2, nhood_size[2] // 2
     d0 = np.random.randint(D, S[2] - D, size=(N, 1, 1, 1, 1))        # same order and shapes as the reference's draws
     x0 = np.random.randint(W, S[4] - W, size=(N, 1, 1, 1, 1))
     y0 = np.random.randint(H, S[3] - H, size=(N, 1, 1, 1, 1))
+    # the reference draws the W centre for a radius of W but moves it by its 2H+1 offsets (and the H centre by the 2W+1
+    # ones): with H != W a neighbourhood can leave the volume.  numpy's flat[idx] wraps or raises there; the kernel would
+    # read foreign memory and cannot see the device-side centres, so this is checked here, before any upload or launch.
+    if x0.min() < H or x0.max() >= S[4] - H or y0.min() < W or y0.max() >= S[3] - W:
+        raise ValueError(f'nhood_size {tuple(nhood_size)}: a drawn neighbourhood leaves the {S[2]} x {S[3]} x {S[4]} volume (the W '
+                         f'centre, drawn from [{W}, {S[4] - W}), carries the {2 * H + 1} offsets of the second size, the H centre, '
+                         f'drawn from [{H}, {S[3] - H}), the {2 * W + 1} of the third)')
+    x = _dev(minibatch)
     t = lambda a: torch.as_tensor(a.reshape(-1).astype(np.int32), device=x.device)
     d0, x0, y0 = t(d0), t(x0), t(y0)
     out = torch.empty((N, S[1], 2 * D + 1, 2 * H + 1, 2 * W + 1), dtype=torch.float32, device=x.device)
