@@ -6,68 +6,28 @@ Tensors keep the reference's logical NCDHW shape (SURFGAN_3D/networks/ops.py:150
 channels-last (torch.channels_last_3d == NDHWC); 2-D tensors [N, F] are NDHWC with one voxel per sample.
 Each backward is itself built from these Functions, so second-order gradients (the gradient penalty of
 networks/loss.py:133-140 differentiates through D's data gradient) work.
+
+Layers, each importing only from those before it (none of them imports this module):
+  0  _lib, _launch (state-free helpers), _scalars (DevCoef, DevScalars)
+  1  _grad_dest (gradient slots, skip_param_grads), _consumers (BackInfo, _note_all), _weight_images (IMAGES: the cached images)
+  2  the leaf domains: loss_ops, augment, mbstd, cond, optim_launch, spectral, guard, table_ops -- they never read a switch
+  3  this module: the _NO_* switches, the raw launches, the conv and elementwise autograd Functions (which call each other by
+     bare name: tests patch them here), the public conv API, and explicit re-exports of every name that lives below.
 """
 import collections
-import contextlib
 import ctypes as C
-import math
 import os
 
 import torch
 
 from . import _lib
+from ._consumers import BackInfo, _note, _note_all
+from ._grad_dest import (_SKIP, _GradOuts, _f32_out, _grad_acc, _note_accumulated, _wants, _zero_scalar,
+                         grads_into as _grads_into)
+from ._launch import _DT, _dims, _dt, _empty_like_shape, _ptr, _req_cuda, _stream, ndhwc
 from ._lib import ConvEpilogue, ConvShape, check
-
-_DT = {torch.float32: _lib.SG_F32, torch.bfloat16: _lib.SG_BF16}
-
-
-def _stream():
-    return C.c_void_p(torch.cuda.current_stream().cuda_stream)
-
-
-def _dt(t):
-    try:
-        return _DT[t.dtype]
-    except KeyError:
-        raise TypeError(f'saragan_amd supports float32 and bfloat16 activations, got {t.dtype}')
-
-
-def _req_cuda(*ts):
-    for t in ts:
-        if t is not None and not t.is_cuda:
-            raise RuntimeError('saragan_amd ops run on the GPU only (no CPU fallback); got a CPU tensor')
-
-
-def ndhwc(x):
-    """Returns x stored as NDHWC (5-D: channels_last_3d; 2-D: row-major)."""
-    if x.dim() == 5:
-        return x.contiguous(memory_format=torch.channels_last_3d)
-    if x.dim() == 2:
-        return x.contiguous()
-    raise ValueError(f'expected a [N,C,D,H,W] or [N,F] tensor, got shape {tuple(x.shape)}')
-
-
-def _dims(x):
-    """-> (n, c, d, h, w) of an NCDHW / [N,F] tensor."""
-    if x.dim() == 5:
-        n, c, d, h, w = x.shape
-        return n, c, d, h, w
-    n, c = x.shape
-    return n, c, 1, 1, 1
-
-
-def _empty_like_shape(x, c_out, spatial=None, dtype=None):
-    n, _, d, h, w = _dims(x)
-    if spatial is not None:
-        d, h, w = spatial
-    dtype = dtype or x.dtype
-    if x.dim() == 5:
-        return torch.empty((n, c_out, d, h, w), device=x.device, dtype=dtype, memory_format=torch.channels_last_3d)
-    return torch.empty((n, c_out), device=x.device, dtype=dtype)
-
-
-def _ptr(t):
-    return C.c_void_p(t.data_ptr()) if t is not None else None
+from ._scalars import DevCoef
+from ._weight_images import IMAGES
 
 
 # ---------------------------------------------------------------------------------------------------
@@ -105,88 +65,30 @@ def _shape(n, d, h, w, cin, cout, k, ups=False):
     return ConvShape(n, d, h, w, cin, cout, k[0], k[1], k[2], 1 if ups else 0)
 
 
-_PACK_CACHE = {}
-_PACK_STATE = {'stale': False}
-PACK_STATS = {'single': 0, 'batches': 0, 'batched': 0}      # counters for the tests (host side only)
-
-
-def clear_pack_cache():
-    """Packed-weight images are reused while the parameter is unchanged (same storage, same version counter): the
-    four discriminator passes and their gradients all read one image per orientation."""
-    _PACK_CACHE.clear()
-    _SUBPIX_CACHE.clear()
-    _PACK_STATE['stale'] = False
+# the cached weight images (_weight_images.IMAGES), by the names they have always had here
+PACK_STATS = IMAGES.stats
+clear_pack_cache = IMAGES.clear
+_packed, _subpixel_packed, _rgb_matrix = IMAGES.fragment, IMAGES.subpixel, IMAGES.rgb_matrix
 
 
 def mark_packs_stale():
-    """The parameters were rewritten behind torch's version counters (the optimiser kernels; a graph capture, which records
-    launches without running them).  The fragment images stay where they are and are rewritten together, one launch for all
-    layers (sg_conv3d_pack_weights_batch), when the next convolution asks for one -- 44 pack launches per step at the
-    benchmarked configuration otherwise.  The few images of other kinds (sub-pixel forms, to_rgb matrices) are dropped and
-    rebuilt on use."""
-    if _NO_PACK_BATCH:
-        return clear_pack_cache()
-    for k in [k for k in _PACK_CACHE if k[0] == 'rgbmat']:
-        del _PACK_CACHE[k]
-    _SUBPIX_CACHE.clear()
-    _PACK_STATE['stale'] = bool(_PACK_CACHE)
+    """WeightImages.mark_stale with the NO_PACK_BATCH switch of the moment; also what the launches below this module that
+    rewrite parameters call (IMAGES.params_rewritten)."""
+    IMAGES.mark_stale(_NO_PACK_BATCH)
+
+
+IMAGES.params_rewritten = mark_packs_stale
 
 
 def live_packs():
     """The cached images and the kept filter-gradient workspaces (tensors): a captured graph whose launches carry their
     addresses keeps them alive -- the caches themselves are released when the next step graph is built."""
-    return [v[0] for v in _PACK_CACHE.values()] + list(_CLEAN_WS.values())
+    return IMAGES.live() + list(_CLEAN_WS.values())
 
 
-def _refresh_packs(lib, st):
-    _PACK_STATE['stale'] = False
-    by_dt = {}
-    for key in list(_PACK_CACHE):
-        if key[0] == 'rgbmat':
-            continue
-        wp, w, shp, w32 = _PACK_CACHE[key]
-        if w._version != key[1] or w.data_ptr() != key[0]:      # modified through torch since: a new key is in use, this one is dead
-            del _PACK_CACHE[key]
-            continue
-        by_dt.setdefault(key[4], []).append((w32, key[2], 1 if key[3] else 0, wp, shp))
-    for dt, items in by_dt.items():
-        n = len(items)
-        ws = (C.c_void_p * n)(*[it[0].data_ptr() for it in items])
-        coefs = (C.c_float * n)(*[it[1] for it in items])
-        flips = (C.c_int * n)(*[it[2] for it in items])
-        wps = (C.c_void_p * n)(*[it[3].data_ptr() for it in items])
-        shapes = (ConvShape * n)(*[it[4] for it in items])
-        check(lib.sg_conv3d_pack_weights_batch(n, ws, coefs, flips, wps, shapes, dt, st), 'sg_conv3d_pack_weights_batch')
-        PACK_STATS['batches'] += 1
-        PACK_STATS['batched'] += n
-
-
-def _packed(w, coef, flip, shp, dt, lib, st):
-    if _PACK_STATE['stale']:
-        _refresh_packs(lib, st)
-    key = (w.data_ptr(), w._version, float(coef), bool(flip), dt, shp.cin, shp.cout, shp.kd, shp.kh, shp.kw)
-    hit = _PACK_CACHE.get(key)
-    if hit is not None:
-        return hit[0]
-    w32 = w.detach()
-    if w32.dtype != torch.float32 or not w32.is_contiguous():
-        w32 = w32.contiguous().float()
-    wp = torch.empty(lib.sg_conv3d_packed_bytes(C.byref(shp), dt), device=w.device, dtype=torch.uint8)
-    check(lib.sg_conv3d_pack_weights(_ptr(w32), float(coef), 1 if flip else 0, _ptr(wp), C.byref(shp), dt, st),
-          'sg_conv3d_pack_weights')
-    PACK_STATS['single'] += 1
-    # only long-lived tensors (parameters) are cached, not transient gradients -- and only f32 contiguous ones are refreshed
-    # in place (w32 aliases the parameter: the batch reads the values of the day)
-    # (a VIEW of a parameter -- the 2-D networks hand [kh, kw, ci, co] filters over as [1, kh, kw, ci, co] -- lives as long as the
-    # parameter and shares its version counter: configs[4] packed its 42 filters 126 times per step before this was recognised)
-    base = w._base if w._is_view() else None
-    long_lived = w.is_leaf or not w.requires_grad or (base is not None and base.is_leaf)
-    if long_lived and w32.data_ptr() == w.data_ptr():
-        keep = ConvShape(shp.n, shp.d, shp.h, shp.w, shp.cin, shp.cout, shp.kd, shp.kh, shp.kw, shp.upsample_in)
-        # holding the tensor keeps its storage (and so the key) from being recycled; for a view its DETACHED alias is held (same
-        # storage, same version counter, no autograd node of the step that made the view)
-        _PACK_CACHE[key] = (wp, w if (w.is_leaf or not w.requires_grad) else w32, keep, w32)
-    return wp
+def grads_into(dest):
+    """_grad_dest.grads_into with the NO_GRAD_DEST switch of the moment."""
+    return _grads_into(dest, not _NO_GRAD_DEST)
 
 
 def _empty_signs(device, n, d, h, w, c):
@@ -210,25 +112,6 @@ def sign_words(t):
     out = _empty_signs(t.device, n, d, h, w, c)
     check(lib.sg_sign_words(_ptr(t), _ptr(out), n * d * h * w, c, _dt(t), _stream()), 'sg_sign_words')
     return out
-
-
-_SUBPIX_CACHE = {}      # summed sub-pixel weight images (see _NO_SUBPIXEL)
-
-
-def _subpixel_packed(w, coef, shp, dt, lib, st):
-    """The summed weights of the eight classes (sg_upconv3d_subpixel_pack), cached like the other packed images."""
-    key = (w.data_ptr(), w._version, float(coef), dt)
-    hit = _SUBPIX_CACHE.get(key)
-    if hit is not None:
-        return hit[0]
-    w32 = w.detach()
-    if w32.dtype != torch.float32 or not w32.is_contiguous():
-        w32 = w32.contiguous().float()
-    wp = torch.empty(lib.sg_upconv3d_subpixel_packed_bytes(C.byref(shp), dt), device=w.device, dtype=torch.uint8)
-    check(lib.sg_upconv3d_subpixel_pack(_ptr(w32), float(coef), _ptr(wp), C.byref(shp), dt, st), 'sg_upconv3d_subpixel_pack')
-    if w.is_leaf or not w.requires_grad:
-        _SUBPIX_CACHE[key] = (wp, w)
-    return wp
 
 
 def _raw_upconv_subpixel(x, w, coef, bias, act, slope, pixel_norm, eps, want_scale, want_signs):
@@ -460,142 +343,6 @@ def raw_bias_act_bwd(dy, y, slope, want_dx=True, want_db=False, b_ptr=0):
 # ---------------------------------------------------------------------------------------------------
 # autograd Functions
 # ---------------------------------------------------------------------------------------------------
-_ZERO = {}
-
-
-def _zero_scalar(like):
-    """A shared 0-d placeholder for 'no bias gradient' outputs (a fresh new_zeros(()) is one fill launch each,
-    ~60 per step)."""
-    z = _ZERO.get(like.device)
-    if z is None:
-        z = _ZERO[like.device] = torch.zeros((), device=like.device, dtype=torch.float32)
-    return z.detach()    # a new tensor object over the same storage: autograd may tag it per Function
-
-
-_SKIP = {'ptrs': frozenset()}
-_GRAD_DEST = {}      # parameter data_ptr -> [f32 view of the step's flat gradient buffer, claimed]
-ACCUMULATED_IN_PLACE = set()   # data_ptr of the parameters whose slot took a later contribution in place during this backward
-GRAD_DEST_STATS = {'claimed': 0, 'accumulated': 0, 'adopted': 0, 'copied': 0, 'unreached': 0}   # counters for the tests (host side only)
-
-
-@contextlib.contextmanager
-def grads_into(dest):
-    """dest: {parameter data_ptr: view of the flat gradient buffer shaped like the parameter}.  Inside this context (the
-    torch.autograd.backward of one training step, optimization.StepGraph._backward) the FIRST weight / bias gradient a
-    backward Function computes for a registered parameter is written by its kernel straight into that view and handed to
-    autograd as such: AccumulateGrad keeps a gradient tensor nobody else holds as .grad, so the parameter's gradient is
-    in the optimiser's buffer without the zero-fill + `add` launch per parameter (71 per step at the benchmarked
-    configuration, 0.37 ms).  Further contributions to the same parameter (the gradient penalty's second-order term of the
-    discriminator's weights) are tensors of their own, summed by autograd; a sum that ended up outside the buffer is
-    copied in by the caller (StepGraph._land)."""
-    prev = dict(_GRAD_DEST)
-    _GRAD_DEST.clear()
-    ACCUMULATED_IN_PLACE.clear()
-    if not _NO_GRAD_DEST:
-        _GRAD_DEST.update({k: [v, False] for k, v in dest.items()})
-    try:
-        yield
-    finally:
-        _GRAD_DEST.clear()
-        _GRAD_DEST.update(prev)
-
-
-def _grad_out(ptr, shape):
-    """A fresh alias (f32, `shape`) of the flat-buffer slot registered for parameter `ptr` if no gradient has been written
-    to it in this backward, else None.  Never while a graph of the backward is being recorded (create_graph)."""
-    if not ptr or not _GRAD_DEST or torch.is_grad_enabled():
-        return None
-    ent = _GRAD_DEST.get(ptr)
-    if ent is None or ent[1] or ent[0].numel() != math.prod(shape):
-        return None
-    ent[1] = True
-    GRAD_DEST_STATS['claimed'] += 1
-    return ent[0].view(shape)
-
-
-def _grad_acc(ptr, shape):
-    """The slot registered for parameter `ptr` when a gradient HAS been written to it in this backward (by a kernel of this
-    module: the alias is with autograd, waiting for the parameter's other contributions) -- a kernel that accumulates
-    (sg_conv3d_wgrad_bias_ex, SG_WGRAD_ACCUMULATE) adds the next contribution in place and the Function returns None for it."""
-    if not ptr or not _GRAD_DEST or torch.is_grad_enabled():
-        return None
-    ent = _GRAD_DEST.get(ptr)
-    if ent is None or not ent[1] or ent[0].numel() != math.prod(shape):
-        return None
-    return ent[0].view(shape)
-
-
-def _note_accumulated(ptr):
-    """A kernel HAS added a contribution in place to the slot of parameter `ptr` (the launch was not declined).  From here on the
-    slot holds more than what autograd was handed: sound only while every later contribution is made in place too -- one that
-    arrives as a tensor of its own makes the engine sum OUT of place (V1 + T2 elsewhere), and copying that sum over the slot would
-    drop what was added here.  StepGraph._land refuses that case."""
-    ACCUMULATED_IN_PLACE.add(ptr)
-    GRAD_DEST_STATS['accumulated'] += 1
-
-
-def _unclaim(ptr, t):
-    """The launch that was to write `t` declined (SG_EUNSUPPORTED: nothing was written) and the caller takes another path: if
-    `t` is the slot of parameter `ptr`, the slot is free again.  (A slot that stayed claimed without being handed to autograd
-    would take later contributions in place -- _grad_acc -- while the parameter's .grad is built from other tensors.)"""
-    ent = _GRAD_DEST.get(ptr) if (ptr and t is not None) else None
-    if ent is not None and ent[1] and t.data_ptr() == ent[0].data_ptr():
-        ent[1] = False
-        GRAD_DEST_STATS['claimed'] -= 1
-
-
-def _f32_out(ptr, shape, device):
-    out = _grad_out(ptr, shape)
-    return out if out is not None else torch.empty(shape, device=device, dtype=torch.float32)
-
-
-class _GradOuts:
-    """The f32 outputs of ONE launch that may decline (SG_EUNSUPPORTED: nothing was written, the caller takes another path).
-    take() hands each one out like _f32_out -- the parameter's slot when it is free, else a fresh tensor; declined(rc) / release()
-    frees exactly the slots that were claimed here (_unclaim says why none may be forgotten), fresh tensors are nobody's business."""
-
-    def __init__(self, device):
-        self.device, self.claimed = device, []
-
-    def take(self, ptr, shape, want=True):
-        if not want:
-            return None
-        out = _grad_out(ptr, shape)
-        if out is None:
-            return torch.empty(shape, device=self.device, dtype=torch.float32)
-        self.claimed.append((ptr, out))
-        return out
-
-    def release(self):
-        for ptr, out in self.claimed:
-            _unclaim(ptr, out)
-        self.claimed = []
-
-    def declined(self, rc):
-        if rc != _lib.SG_EUNSUPPORTED:
-            return False
-        self.release()
-        return True
-
-
-@contextlib.contextmanager
-def skip_param_grads(params):
-    """Inside this context the backward Functions do not compute gradients of the given parameters.
-    `ctx.needs_input_grad` is True for every weight that requires grad, also when the caller asked autograd for other
-    inputs only (the gradient-penalty d D/d x pass, networks/loss.py:136-139; the generator loss flowing through the
-    discriminator, optimization.py:128-163): the weight/bias-gradient kernels would run and their results be dropped."""
-    prev = _SKIP['ptrs']
-    _SKIP['ptrs'] = prev | frozenset(p.data_ptr() for p in params)
-    try:
-        yield
-    finally:
-        _SKIP['ptrs'] = prev
-
-
-def _wants(ctx, i, ptr):
-    return ctx.needs_input_grad[i] and ptr not in _SKIP['ptrs']
-
-
 class ActInfo:
     """Bookkeeping of one LeakyReLU output `a` (created by the layer that produced it).  Consumers that are able
     to apply the LeakyReLU-backward mask where(a >= 0, g, slope*g) inside THEIR backward kernel (the data-gradient
@@ -693,43 +440,9 @@ def _pw_fused_backward(info, g, w, coef, flip):
     return torch.zeros((), device=g.device, dtype=g.dtype).expand(n, w.shape[3] if flip else w.shape[4], d, h, wd)
 
 
-class BackInfo:
-    """The same bookkeeping one order up.  `t = M * conv(x)` (a data-gradient conv with a LeakyReLU mask in its epilogue,
-    created while the gradient penalty's first backward builds its graph) has the backward gy -> M * gy, a full pass over
-    the tensor.  Every Function that consumes `t` registers here (forward time); consumers that are able to return
-    M * (their gradient) from their own kernel -- a conv's mask epilogue -- register as `premask`.  If all of them did,
-    they do, and the producer skips its pass (decided at backward time, when all consumers are known).  Functions of this
-    module are the only consumers of such tensors; all of them call _note_consumer on their tensor inputs."""
-
-    def __init__(self, bits, slope):
-        self.bits, self.slope = bits, float(slope)
-        self.n_consumers = 0
-        self.n_premask = 0
-        self._decision = None
-
-    def all_premask(self):
-        # decided once, by whoever asks first (a consumer's backward runs before the producer's): the backward itself
-        # hands the tensor to further Functions (the weight gradient of the double backward), which must not change
-        # what the consumers that already ran were told
-        if self._decision is None:
-            self._decision = self.n_consumers > 0 and self.n_consumers == self.n_premask
-        return self._decision
-
-
 def _note_consumer(t, premask=False):
-    info = getattr(t, '_sg_back', None) if t is not None else None
-    if info is not None and info._decision is None:
-        info.n_consumers += 1
-        if premask and not _NO_BACK_PREMASK:
-            info.n_premask += 1
-    return info
-
-
-def _note_all(*args):
-    """A Function without a mask epilogue consuming the output of a masked conv: counted, never pre-masking."""
-    for a in args:
-        if isinstance(a, torch.Tensor):
-            _note_consumer(a)
+    """Counts this Function as a consumer of t (a masked conv's output: BackInfo), pre-masking if it says so; -> the BackInfo."""
+    return _note(t, premask and not _NO_BACK_PREMASK)
 
 
 def _conv_dgrad(g, w, coef, flip, ups=False, in_info=None, x_back=None):
@@ -882,20 +595,6 @@ class _ConvBiasAct(torch.autograd.Function):
             gx = _conv_dgrad(g, w, coef, True, ups, ctx.in_info)
         gw, gb = _conv_param_grads(x, g, w, coef, ups, _wants(ctx, 1, w.data_ptr()), want_db, ctx.b_ptr, gb)
         return gx, gw, gb, None, None, None, None, None, None, None, None
-
-
-def _rgb_matrix(w_rgb, coef, dtype, small_is_cin=False):
-    """[cs][c] f32 of a pointwise convolution between cs <= 4 and c channels: the values its forward multiplied with
-    (coef * w rounded to the compute dtype, as the packed weight image holds them), for sg_pixel_norm_act_bwd_pw (to_rgb:
-    cs = cout) and sg_conv3d_pw_bwd (from_rgb: cs = cin).  Cached like the packed images."""
-    key = ('rgbmat', w_rgb.data_ptr(), w_rgb._version, float(coef), dtype, small_is_cin)
-    hit = _PACK_CACHE.get(key)
-    if hit is not None:
-        return hit[0]
-    m = (w_rgb.detach().reshape(w_rgb.shape[-2], w_rgb.shape[-1]).float() * float(coef)).to(dtype).float()
-    m = (m if small_is_cin else m.t()).contiguous()
-    _PACK_CACHE[key] = (m, w_rgb)
-    return m
 
 
 def _pw_backward(x, dy, w, coef, want_db, b_ptr=0):
@@ -1278,18 +977,7 @@ def _upconv_dgrad_subpixel(g, w, coef):
     low = _shape(n, d2 // 2, h2 // 2, w2 // 2, ci, co, (3, 3, 3), False)
     if not lib.sg_upconv3d_subpixel_dgrad_supported(C.byref(low), dt):
         return None
-    key = ('subpix_dgrad', w.data_ptr(), w._version, float(coef), dt)
-    hit = _SUBPIX_CACHE.get(key)
-    if hit is None:
-        w32 = w.detach()
-        if w32.dtype != torch.float32 or not w32.is_contiguous():
-            w32 = w32.contiguous().float()
-        wp = torch.empty(lib.sg_upconv3d_subpixel_dgrad_packed_bytes(C.byref(low), dt), device=w.device, dtype=torch.uint8)
-        check(lib.sg_upconv3d_subpixel_dgrad_pack(_ptr(w32), float(coef), _ptr(wp), C.byref(low), dt, st), 'sg_upconv3d_subpixel_dgrad_pack')
-        if w.is_leaf or not w.requires_grad:
-            _SUBPIX_CACHE[key] = (wp, w)
-    else:
-        wp = hit[0]
+    wp = _subpixel_packed(w, coef, low, dt, lib, st, dgrad=True)
     gx = _empty_like_shape(g, ci, (d2 // 2, h2 // 2, w2 // 2))
     rc = lib.sg_upconv3d_subpixel_dgrad(_ptr(g), _ptr(wp), _ptr(gx), C.byref(low), dt, st)
     if rc == _lib.SG_EUNSUPPORTED:
@@ -1533,63 +1221,6 @@ class _TriUp(torch.autograd.Function):
         return _TriUp.apply(gy, not ctx.adjoint), None
 
 
-class DevCoef(float):
-    """A step scalar that ALSO lives in device memory (element `idx` of `buf`, f32): the value a kernel of a captured step
-    reads (sg_axpby_dev, sg_adam_ema_dev).  Behaves as its host value everywhere else."""
-
-    def __new__(cls, value, buf, idx):
-        o = float.__new__(cls, value)
-        o.buf, o.idx = buf, int(idx)
-        return o
-
-    def ptr(self):
-        return C.c_void_p(self.buf.data_ptr() + self.buf.element_size() * self.idx)
-
-
-class DevScalars:
-    """The per-step scalars of a captured step (optimization.StepGraph): fade-in weights [alpha, 1 - alpha] and the step size
-    of each optimiser.  The host writes them into a pinned mirror (`set`) and `flush()` sends all of them with one
-    asynchronous copy before the graph is replayed; the captured kernels read the device copy.  The values are the f32
-    roundings of the doubles the eager path hands to ctypes: the same bits reach the same arithmetic.
-    A replayed step costs the host next to nothing, so it runs ahead of the device: the pinned source of a copy that has not
-    executed yet must not be rewritten (with ONE mirror a replay could read the alpha / step size of a later
-    step).  The mirror is a ring of pinned slots, each with the event recorded behind its last copy; a slot is rewritten only
-    after that event (the host waits only if it is RING flushes ahead)."""
-    RING = 8
-
-    def __init__(self, device, n=8, dtype=torch.float32):
-        cuda = torch.device(device).type == 'cuda'
-        self._ring = [torch.zeros(n, dtype=dtype).pin_memory() if cuda else torch.zeros(n, dtype=dtype)
-                      for _ in range(self.RING if cuda else 1)]
-        self._events = [None] * len(self._ring)
-        self._cur = 0
-        self.host = self._ring[0]
-        self.dev = torch.zeros(n, dtype=dtype, device=device)
-        self.waits = 0            # times the host had to wait for a slot (tests)
-
-    def set(self, idx, value):
-        self.host[idx] = float(value)
-
-    def coef(self, idx, value):
-        self.set(idx, value)
-        return DevCoef(value, self.dev, idx)
-
-    def flush(self):
-        self.dev.copy_(self.host, non_blocking=True)
-        if len(self._ring) == 1:
-            return
-        ev = self._events[self._cur]
-        if ev is None:
-            ev = self._events[self._cur] = torch.cuda.Event()
-        ev.record()
-        nxt = (self._cur + 1) % len(self._ring)
-        if self._events[nxt] is not None and not self._events[nxt].query():
-            self._events[nxt].synchronize()
-            self.waits += 1
-        self._ring[nxt].copy_(self.host)      # values not set again keep theirs
-        self._cur, self.host = nxt, self._ring[nxt]
-
-
 class _Axpby(torch.autograd.Function):
     """out = wa*a + wb*b (fade-in lerp, pgan/generator.py:100-101, pgan/discriminator.py:105)."""
 
@@ -1621,112 +1252,6 @@ class _Axpby(torch.autograd.Function):
         ga = scaled(ctx.wa) if ctx.needs_input_grad[0] else None
         gb = scaled(ctx.wb) if (ctx.has_b and ctx.needs_input_grad[1]) else None
         return ga, gb, None, None
-
-
-class _AddNoise(torch.autograd.Function):
-    @staticmethod
-    def forward(ctx, x, stddev, seed, offset):
-        """offset: a Python int, or a one-element int64 DEVICE tensor holding the Philox offset (read by the kernel and then
-        advanced by 1 << 40 on the device: the form a captured step uses, sg_add_noise_dev)."""
-        _note_all(x, stddev, seed, offset)
-        lib = _lib.load()
-        _req_cuda(x)
-        x = ndhwc(x)
-        out = torch.empty_like(x)
-        if torch.is_tensor(offset):
-            check(lib.sg_add_noise_dev(_ptr(x), _ptr(out), float(stddev), int(seed), _ptr(offset), 1 << 40, x.numel(), _dt(x),
-                                       _stream()), 'sg_add_noise_dev')
-        else:
-            check(lib.sg_add_noise(_ptr(x), _ptr(out), float(stddev), int(seed), int(offset), x.numel(), _dt(x),
-                                   _stream()), 'sg_add_noise')
-        return out
-
-    @staticmethod
-    def backward(ctx, g):
-        return g, None, None, None
-
-
-class _Augment(torch.autograd.Function):
-    """sg_augment_apply: per-sample flips / rot90 / integer translation of an NDHWC batch (forward), or its exact adjoint.
-    The derivative of either with respect to x is the other one with fill 0, so the backward is this Function again with the
-    flag flipped: differentiable to any order (the gradient penalty differentiates through D's data gradient)."""
-
-    @staticmethod
-    def forward(ctx, x, params, fill, ops, adjoint):
-        _note_all(x, params)
-        lib = _lib.load()
-        _req_cuda(x, params)
-        if x.dim() != 5:
-            raise ValueError(f'augment takes a [N,C,D,H,W] tensor, got shape {tuple(x.shape)}')
-        x = ndhwc(x)
-        n, c, d, h, w = _dims(x)
-        if params.dtype != torch.int32 or tuple(params.shape) != (n, 8) or not params.is_contiguous():
-            raise ValueError(f'augment parameters are a contiguous int32 [{n}, 8] tensor, got {params.dtype} {tuple(params.shape)}')
-        y = torch.empty_like(x)
-        check(lib.sg_augment_apply(_ptr(x), _ptr(y), _ptr(params), n, d, h, w, c, int(ops), float(fill), 1 if adjoint else 0,
-                                   _dt(x), _stream()), 'sg_augment_apply')
-        ctx.save_for_backward(params)
-        ctx.ops, ctx.adjoint = int(ops), bool(adjoint)
-        return y
-
-    @staticmethod
-    def backward(ctx, g):
-        (params,) = ctx.saved_tensors
-        return _Augment.apply(g, params, 0.0, ctx.ops, not ctx.adjoint), None, None, None, None
-
-
-class _AugmentAffine(torch.autograd.Function):
-    """sg_augment_affine_apply: per-sample trilinear resampling of an NDHWC batch by a 3 x 4 matrix with gain and bias (forward),
-    or the exact adjoint of its linear part.  The derivative of either direction with respect to x is the other one with the
-    LINEAR flag (fill and bias read as 0), so the backward is this Function again: differentiable to any order."""
-
-    @staticmethod
-    def forward(ctx, x, params, fill, adjoint, linear):
-        _note_all(x, params)
-        lib = _lib.load()
-        _req_cuda(x, params)
-        if x.dim() != 5:
-            raise ValueError(f'augment_affine takes a [N,C,D,H,W] tensor, got shape {tuple(x.shape)}')
-        x = ndhwc(x)
-        n, c, d, h, w = _dims(x)
-        if params.dtype != torch.float32 or tuple(params.shape) != (n, 16) or not params.is_contiguous():
-            raise ValueError(f'augment_affine parameters are a contiguous float32 [{n}, 16] tensor, got {params.dtype} '
-                             f'{tuple(params.shape)}')
-        y = torch.empty_like(x)
-        flags = (_lib.SG_AUGF_ADJOINT if adjoint else 0) | (_lib.SG_AUGF_LINEAR if linear else 0)
-        check(lib.sg_augment_affine_apply(_ptr(x), _ptr(y), _ptr(params), n, d, h, w, c, float(fill), flags, _dt(x), _stream()),
-              'sg_augment_affine_apply')
-        ctx.save_for_backward(params)
-        ctx.adjoint = bool(adjoint)
-        return y
-
-    @staticmethod
-    def backward(ctx, g):
-        (params,) = ctx.saved_tensors
-        return _AugmentAffine.apply(g, params, 0.0, not ctx.adjoint, True), None, None, None, None
-
-
-class _SumsqKeepW(torch.autograd.Function):
-    """out[n, w] = sum_{c,d,h} g^2: tf.reduce_sum(tf.square(g), (1,2,3)) on NCDHW (networks/loss.py:140)."""
-
-    @staticmethod
-    def forward(ctx, g):
-        _note_all(g)
-        lib = _lib.load()
-        _req_cuda(g)
-        g = ndhwc(g)
-        n, c, d, h, w = _dims(g)
-        out = torch.empty((n, w), device=g.device, dtype=torch.float32)
-        check(lib.sg_sumsq_ndhwc_keep_w(_ptr(g), _ptr(out), n, d, h, w, c, _dt(g), _stream()),
-              'sg_sumsq_ndhwc_keep_w')
-        ctx.save_for_backward(g)
-        return out
-
-    @staticmethod
-    def backward(ctx, gout):
-        (g,) = ctx.saved_tensors
-        n, w = gout.shape
-        return (2.0 * gout.reshape(n, 1, 1, 1, w)).to(g.dtype) * g
 
 
 # ---------------------------------------------------------------------------------------------------
@@ -1781,852 +1306,22 @@ def lerp(a, b, wa, wb):
     return _Axpby.apply(a, b, wa, wb)
 
 
-def interpolate_rows(gamma, a, b):
-    """gamma * a + (1 - gamma) * b with one weight per batch sample (gamma: [N, 1, 1, 1, 1] or [N], f32): the gradient
-    penalty's interpolates (networks/loss.py:70-71, :133-134) in ONE launch with one rounding (sg_lerp_rows).  No gradient:
-    every caller detaches the result (the penalty differentiates with respect to the interpolates, not through them)."""
-    lib = _lib.load()
-    _req_cuda(a, b, gamma)
-    a, b = ndhwc(a.detach()), ndhwc(b.detach())
-    if a.shape != b.shape or a.dtype != b.dtype:
-        raise ValueError('interpolate_rows: operands differ in shape or dtype')
-    g = gamma.detach().reshape(-1).float().contiguous()
-    if g.numel() != a.shape[0]:
-        raise ValueError('interpolate_rows: one weight per batch sample')
-    out = torch.empty_like(a)
-    check(lib.sg_lerp_rows(_ptr(a), _ptr(b), _ptr(g), _ptr(out), a.shape[0], a.numel() // a.shape[0], _dt(a), _stream()),
-          'sg_lerp_rows')
-    return out
+# ---------------------------------------------------------------------------------------------------
+# what lives in the layers below, under the names it has always had here (the same objects: state is only mutated in place)
+# ---------------------------------------------------------------------------------------------------
+from ._grad_dest import (_GRAD_DEST, _ZERO, ACCUMULATED_IN_PLACE, GRAD_DEST_STATS, _grad_out, _unclaim,  # noqa: E402,F401
+                         skip_param_grads)
+from ._scalars import DevScalars, _dev_ptr  # noqa: E402,F401
+from .augment import (AUG_ALL, AUG_OPS, AUGF_ALL, _Augment, _AugmentAffine, ada_update_, augment, augment_affine,  # noqa: E402,F401
+                      augment_affine_draw, augment_draw, augment_ops_mask)
+from .cond import _CondEmbed, _CondProject, cond_embed, cond_project  # noqa: E402,F401
+from .guard import guard_step_, nonfinite_flag_, segment_sumsq  # noqa: E402,F401
+from .loss_ops import _AddNoise, _SumsqKeepW, add_noise, interpolate_rows, sumsq_keep_w  # noqa: E402,F401
+from .mbstd import (_MBSTD_MASKS, _MbstdDot, _MbstdOuter, _MbstdPlane, _MbstdStat, _MbstdStatBwd, _MbstdTerm,  # noqa: E402,F401
+                    _MinibatchStddev, mbstd_plane, mbstd_stat, mbstd_tap_mask, mbstd_term, minibatch_stddev)
+from .optim_launch import (SegmentTable, adam_ema_, adam_step_size, adamw_ema_, lamb_ema_, optim_step_,  # noqa: E402,F401
+                           segment_table_arrays)
+from .spectral import (SPECTRAL_MAX_BLOCKS, SPECTRAL_MIN_ROWS, SpectralTable, spectral_pullback_, spectral_refresh_,  # noqa: E402,F401
+                       spectral_rows_per_block, spectral_table_arrays)
+from .table_ops import HIST_DT as _HIST_DT, SRC_DT as _SRC_DT, check_positions, gather_rows, intensity_hist  # noqa: E402,F401
 
-
-def add_noise(x, stddev, seed, offset=0):
-    return _AddNoise.apply(x, stddev, seed, offset)
-
-
-AUG_OPS = {'flip_w': _lib.SG_AUG_FLIP_W, 'flip_h': _lib.SG_AUG_FLIP_H, 'flip_d': _lib.SG_AUG_FLIP_D, 'rot90': _lib.SG_AUG_ROT90,
-           'translate': _lib.SG_AUG_TRANSLATE, 'scale': _lib.SG_AUGF_SCALE, 'rotate': _lib.SG_AUGF_ROTATE,
-           'shift': _lib.SG_AUGF_SHIFT, 'brightness': _lib.SG_AUGF_BRIGHTNESS, 'contrast': _lib.SG_AUGF_CONTRAST}
-AUG_ALL = _lib.SG_AUG_ALL            # the pixel-blitting transforms (sg_augment_draw / sg_augment_apply)
-AUGF_ALL = _lib.SG_AUGF_ALL          # the intensity and fractional-geometry transforms (sg_augment_affine_*)
-
-
-def augment_ops_mask(names):
-    """'flip_w,translate' (or a list of names) -> the combined SG_AUG_* | SG_AUGF_* bit mask (mask & AUG_ALL goes to the blitting
-    entry points, mask & AUGF_ALL to the affine ones)."""
-    if isinstance(names, str):
-        names = [s for s in names.split(',') if s]
-    mask = 0
-    for name in names:
-        if name not in AUG_OPS:
-            raise ValueError(f'unknown augmentation {name!r}: choose from {", ".join(AUG_OPS)}')
-        mask |= AUG_OPS[name]
-    return mask
-
-
-def augment_draw(n, ops, max_shift, p, seed, offset=0, device=None):
-    """Per-sample augmentation parameters, int32 [n, 8] = {flip_d, flip_h, flip_w, rot_k, t_d, t_h, t_w, 0}, drawn on the device
-    (sg_augment_draw; the rule is in include/saragan_hip.h).  ops: SG_AUG_* mask; max_shift: (m_d, m_h, m_w).  p: a Python
-    float, or a one-element f32 DEVICE tensor the kernel reads.  offset: a Python int, or a one-element int64 DEVICE tensor
-    read by the kernel and then advanced by 1 << 40 on the device (the forms a captured step uses)."""
-    lib = _lib.load()
-    for t in (p, offset):
-        if torch.is_tensor(t):
-            _req_cuda(t)
-            device = device or t.device
-    out = torch.empty((int(n), 8), dtype=torch.int32, device=device or 'cuda')
-    _req_cuda(out)
-    m_d, m_h, m_w = (int(m) for m in max_shift)
-    p_dev = torch.is_tensor(p)
-    if p_dev and (p.dtype != torch.float32 or p.numel() != 1):
-        raise ValueError('a device-side probability is a one-element float32 tensor')
-    off_dev = torch.is_tensor(offset)
-    if off_dev and (offset.dtype != torch.int64 or offset.numel() != 1):
-        raise ValueError('a device-side Philox offset is a one-element int64 tensor')
-    check(lib.sg_augment_draw(_ptr(out), int(n), int(ops), m_d, m_h, m_w, 0.0 if p_dev else float(p), _ptr(p) if p_dev else None,
-                              int(seed) & (2 ** 64 - 1), 0 if off_dev else int(offset) & (2 ** 64 - 1),
-                              _ptr(offset) if off_dev else None, (1 << 40) if off_dev else 0, _stream()), 'sg_augment_draw')
-    return out
-
-
-def augment(x, params, fill=0.0, ops=AUG_ALL, adjoint=False):
-    """y[i] = shift(rot90(flip(x[i], axes), k, plane (h, w)), t, fill) with sample i's `params` row (augment_draw's layout);
-    adjoint=True: the exact transpose of its linear part.  Only the transforms in `ops` are read from params; rot90 needs
-    h == w.  Values are copied: a permutation reproduces x's bits."""
-    return _Augment.apply(x, params, fill, ops, adjoint)
-
-
-def augment_affine_draw(n, ops, extent, p, seed, offset=0, max_scale=1.25, max_angle=math.pi, max_shift=(0.0, 0.0, 0.0),
-                        max_brightness=0.2, max_contrast=1.5, device=None, bump=1 << 40):
-    """Per-sample affine augmentation parameters, float32 [n, 16] = {row-major 3 x 4 source matrix, gain, bias, 0, 0}, drawn on
-    the device (sg_augment_affine_draw; the rule is in include/saragan_hip.h).  ops: SG_AUGF_* mask; extent: (d, h, w) of the
-    volumes the rows are for; max_angle in radians; max_shift: (m_d, m_h, m_w) in voxels, fractions allowed.  p and offset as
-    augment_draw; a device offset is advanced by `bump` after it is read (0: a blitting draw that follows reads the same offset
-    and advances it)."""
-    lib = _lib.load()
-    for t in (p, offset):
-        if torch.is_tensor(t):
-            _req_cuda(t)
-            device = device or t.device
-    out = torch.empty((int(n), 16), dtype=torch.float32, device=device or 'cuda')
-    _req_cuda(out)
-    d, h, w = (int(e) for e in extent)
-    m_d, m_h, m_w = (float(m) for m in max_shift)
-    p_dev = torch.is_tensor(p)
-    if p_dev and (p.dtype != torch.float32 or p.numel() != 1):
-        raise ValueError('a device-side probability is a one-element float32 tensor')
-    off_dev = torch.is_tensor(offset)
-    if off_dev and (offset.dtype != torch.int64 or offset.numel() != 1):
-        raise ValueError('a device-side Philox offset is a one-element int64 tensor')
-    check(lib.sg_augment_affine_draw(_ptr(out), int(n), int(ops), d, h, w, float(max_scale), float(max_angle), m_d, m_h, m_w,
-                                     float(max_brightness), float(max_contrast), 0.0 if p_dev else float(p),
-                                     _ptr(p) if p_dev else None, int(seed) & (2 ** 64 - 1),
-                                     0 if off_dev else int(offset) & (2 ** 64 - 1), _ptr(offset) if off_dev else None,
-                                     int(bump) if off_dev else 0, _stream()), 'sg_augment_affine_draw')
-    return out
-
-
-def augment_affine(x, params, fill=0.0, adjoint=False):
-    """y[i] = trilinear resampling of x[i] at u = A v + t with gain and bias, sample i's `params` row (augment_affine_draw's
-    layout; source voxels outside the volume read `fill`); adjoint=True: the exact transpose of its linear part, a gather in a
-    fixed order (no atomics).  An identity row reproduces x's bits."""
-    return _AugmentAffine.apply(x, params, fill, adjoint, bool(adjoint))
-
-
-def ada_update_(logits, state, p, interval, target, delta, p_max):
-    """The adaptive augmentation probability's controller (sg_ada_update, one thread; rule in include/saragan_hip.h).
-    logits: D's outputs on the real batch; state: int64 [4] {sum_sign, count, steps, adjustments}; p: f32 [1] (device tensors,
-    updated in place).  target: (numerator, denominator) of the sign statistic's set point."""
-    lib = _lib.load()
-    _req_cuda(logits, state, p)
-    lg = logits.detach().reshape(-1)
-    if lg.dtype != torch.float32 or not lg.is_contiguous():
-        lg = lg.float().contiguous()
-    if state.dtype != torch.int64 or state.numel() != 4 or p.dtype != torch.float32 or p.numel() != 1:
-        raise ValueError('ada_update_: state is int64 [4], p is float32 [1]')
-    check(lib.sg_ada_update(_ptr(lg), lg.numel(), _ptr(state), _ptr(p), int(interval), int(target[0]), int(target[1]),
-                            float(delta), float(p_max), _stream()), 'sg_ada_update')
-
-
-def sumsq_keep_w(g):
-    return _SumsqKeepW.apply(g)
-
-
-class _MinibatchStddev(torch.autograd.Function):
-    """networks/ops.py:313-325: concat(x, per-group mean stddev).  Once-differentiable (the layer is disabled in
-    pgan, pgan/discriminator.py:50, so it never sits under the gradient penalty)."""
-
-    @staticmethod
-    def forward(ctx, x, group_size):
-        _note_all(x, group_size)
-        lib = _lib.load()
-        _req_cuda(x)
-        x = ndhwc(x)
-        n, c, d, h, w = _dims(x)
-        g = min(group_size, n)
-        if n % g != 0:
-            raise ValueError(f'minibatch_stddev_layer: batch {n} not divisible by group {g}')
-        y = _empty_like_shape(x, c + 1)
-        ws = torch.empty(n // g, device=x.device, dtype=torch.float32)
-        check(lib.sg_minibatch_stddev_fwd(_ptr(x), _ptr(y), _ptr(ws), n, d * h * w, c, group_size, _dt(x), _stream()),
-              'sg_minibatch_stddev_fwd')
-        ctx.save_for_backward(x)
-        ctx.group_size = group_size
-        return y
-
-    @staticmethod
-    @torch.autograd.function.once_differentiable
-    def backward(ctx, gy):
-        lib = _lib.load()
-        (x,) = ctx.saved_tensors
-        gy = ndhwc(gy)
-        n, c, d, h, w = _dims(x)
-        g = min(ctx.group_size, n)
-        dx = torch.empty_like(x)
-        ws = torch.empty(n // g, device=x.device, dtype=torch.float32)
-        check(lib.sg_minibatch_stddev_bwd(_ptr(gy), _ptr(x), _ptr(dx), _ptr(ws), n, d * h * w, c, ctx.group_size, _dt(x),
-                                          _stream()), 'sg_minibatch_stddev_bwd')
-        return dx, None
-
-
-def minibatch_stddev(x, group_size=4):
-    """networks/ops.py:313-325 (the layer is disabled in pgan, pgan/discriminator.py:50)."""
-    return _MinibatchStddev.apply(x, group_size)
-
-
-# ---- minibatch standard deviation without the concatenation (DESIGN.md 4.3): the statistic as N floats, twice differentiable,
-# and the rank-1 term it adds to the convolution that follows.  Every backward is a Function of this group again.
-def _mbstd_ws(lib, x, n, vox, c, group, nseg):
-    nbytes = int(lib.sg_mbstd_stat_workspace(n, vox, c, group, nseg))      # (0: a batch the groups do not divide -- the launch refuses)
-    return torch.empty(nbytes // 4, device=x.device, dtype=torch.float32), nbytes
-
-
-class _MbstdStat(torch.autograd.Function):
-    """stat[n] (f32): the mean over a sample's positions of the standard deviation over its group (sg_mbstd_stat_fwd)."""
-
-    @staticmethod
-    def forward(ctx, x, group, nseg):
-        _note_all(x)
-        lib = _lib.load()
-        _req_cuda(x)
-        ctx.save_for_backward(x)      # (the inputs themselves are saved throughout this group: the backward Functions take them as
-        x = ndhwc(x)                  # inputs again, and a converted copy would cut the second-order graph)
-        n, c, d, h, w = _dims(x)
-        stat = torch.empty(n, device=x.device, dtype=torch.float32)
-        ws, nbytes = _mbstd_ws(lib, x, n, d * h * w, c, group, nseg)
-        check(lib.sg_mbstd_stat_fwd(_ptr(x), _ptr(stat), _ptr(ws), nbytes, n, d * h * w, c, group, nseg, _dt(x), _stream()),
-              'sg_mbstd_stat_fwd')
-        ctx.group, ctx.nseg = group, nseg
-        return stat
-
-    @staticmethod
-    def backward(ctx, gstat):
-        (x,) = ctx.saved_tensors
-        return _MbstdStatBwd.apply(gstat, x, ctx.group, ctx.nseg), None, None
-
-
-class _MbstdStatBwd(torch.autograd.Function):
-    """dx of _MbstdStat (sg_mbstd_stat_bwd); its own backward is sg_mbstd_stat_bwd2, which ends the chain: nothing in the step
-    differentiates a third time."""
-
-    @staticmethod
-    def forward(ctx, gstat, x, group, nseg):
-        _note_all(gstat, x)
-        lib = _lib.load()
-        ctx.save_for_backward(gstat, x)
-        gstat, x = gstat.contiguous().float(), ndhwc(x)
-        n, c, d, h, w = _dims(x)
-        dx = torch.empty_like(x)
-        check(lib.sg_mbstd_stat_bwd(_ptr(gstat), _ptr(x), _ptr(dx), n, d * h * w, c, group, nseg, _dt(x), _stream()),
-              'sg_mbstd_stat_bwd')
-        ctx.group, ctx.nseg = group, nseg
-        return dx
-
-    @staticmethod
-    @torch.autograd.function.once_differentiable
-    def backward(ctx, hh):
-        lib = _lib.load()
-        gstat, x = ctx.saved_tensors
-        want_gg, want_gx = ctx.needs_input_grad[0], ctx.needs_input_grad[1]
-        if not (want_gg or want_gx):
-            return None, None, None, None
-        gstat, x = gstat.contiguous().float(), ndhwc(x)
-        hh = ndhwc(hh.to(x.dtype))
-        n, c, d, h, w = _dims(x)
-        gx = torch.empty_like(x) if want_gx else None
-        ggstat = torch.empty(n, device=x.device, dtype=torch.float32) if want_gg else None
-        ws, nbytes = _mbstd_ws(lib, x, n, d * h * w, c, ctx.group, ctx.nseg) if want_gg else (None, 0)
-        check(lib.sg_mbstd_stat_bwd2(_ptr(hh), _ptr(x), _ptr(gstat), _ptr(gx), _ptr(ggstat), _ptr(ws), nbytes, n, d * h * w, c,
-                                     ctx.group, ctx.nseg, _dt(x), _stream()), 'sg_mbstd_stat_bwd2')
-        return ggstat, gx, None, None
-
-
-def _plane_numel(shape):
-    return math.prod(shape[1:])
-
-
-class _MbstdTerm(torch.autograd.Function):
-    """out = y + s (x) B (sg_mbstd_term_fwd): y [N,C,D,H,W] (None: the outer product alone, shaped `shape`, of `dtype`),
-    s f32 [N], B f32 [D,H,W,C].  w_ptr: the data_ptr of the weight B was made from (0: none), for skip_param_grads."""
-
-    @staticmethod
-    def forward(ctx, y, s, B, w_ptr, shape, dtype):
-        _note_all(y, s, B)
-        lib = _lib.load()
-        _req_cuda(s, B)
-        ctx.save_for_backward(s, B)
-        if y is not None:
-            y = ndhwc(y)
-            shape, dtype = tuple(y.shape), y.dtype
-        s, B = s.contiguous().float(), B.contiguous().float()
-        if B.numel() != _plane_numel(shape) or s.numel() != shape[0]:
-            raise ValueError(f'mbstd_term: s {tuple(s.shape)} / B {tuple(B.shape)} do not fit the tensor {tuple(shape)}')
-        out = torch.empty(shape, device=s.device, dtype=dtype, memory_format=torch.channels_last_3d)
-        check(lib.sg_mbstd_term_fwd(_ptr(y), _ptr(s), _ptr(B), _ptr(out), shape[0], B.numel(), _DT[dtype], _stream()),
-              'sg_mbstd_term_fwd')
-        ctx.w_ptr = w_ptr
-        return out
-
-    @staticmethod
-    def backward(ctx, gout):
-        s, B = ctx.saved_tensors
-        gy = gout if ctx.needs_input_grad[0] else None
-        gs = _MbstdDot.apply(gout, B, ctx.w_ptr) if ctx.needs_input_grad[1] else None
-        gB = _MbstdOuter.apply(s, gout) if _wants(ctx, 2, ctx.w_ptr) else None
-        return gy, gs, gB, None, None, None
-
-
-class _MbstdDot(torch.autograd.Function):
-    """r[n] = <g[n], B> (sg_mbstd_term_dot), f32 [N]."""
-
-    @staticmethod
-    def forward(ctx, g, B, w_ptr):
-        _note_all(g, B)
-        lib = _lib.load()
-        _req_cuda(g, B)
-        ctx.save_for_backward(g, B)
-        g, B = ndhwc(g), B.contiguous().float()
-        if B.numel() != _plane_numel(g.shape):
-            raise ValueError(f'mbstd: B {tuple(B.shape)} does not fit the tensor {tuple(g.shape)}')
-        r = torch.empty(g.shape[0], device=g.device, dtype=torch.float32)
-        check(lib.sg_mbstd_term_dot(_ptr(g), _ptr(B), _ptr(r), g.shape[0], B.numel(), _dt(g), _stream()), 'sg_mbstd_term_dot')
-        ctx.w_ptr = w_ptr
-        return r
-
-    @staticmethod
-    def backward(ctx, gr):
-        g, B = ctx.saved_tensors
-        gg = _MbstdTerm.apply(None, gr, B, ctx.w_ptr, tuple(g.shape), g.dtype) if ctx.needs_input_grad[0] else None
-        gB = _MbstdOuter.apply(gr, g) if _wants(ctx, 1, ctx.w_ptr) else None
-        return gg, gB, None
-
-
-class _MbstdOuter(torch.autograd.Function):
-    """Bg = sum_n s_n g[n] (sg_mbstd_term_outer), f32 [D,H,W,C], n ascending."""
-
-    @staticmethod
-    def forward(ctx, s, g):
-        _note_all(s, g)
-        lib = _lib.load()
-        _req_cuda(s, g)
-        ctx.save_for_backward(s, g)
-        s, g = s.contiguous().float(), ndhwc(g)
-        n, c, d, h, w = _dims(g)
-        if s.numel() != n:
-            raise ValueError(f'mbstd: s {tuple(s.shape)} does not fit the tensor {tuple(g.shape)}')
-        Bg = torch.empty((d, h, w, c), device=g.device, dtype=torch.float32)
-        check(lib.sg_mbstd_term_outer(_ptr(s), _ptr(g), _ptr(Bg), n, Bg.numel(), _dt(g), _stream()), 'sg_mbstd_term_outer')
-        return Bg
-
-    @staticmethod
-    def backward(ctx, gBg):
-        s, g = ctx.saved_tensors
-        gs = _MbstdDot.apply(g, gBg, 0) if ctx.needs_input_grad[0] else None
-        gg = _MbstdTerm.apply(None, s, gBg, 0, tuple(g.shape), g.dtype) if ctx.needs_input_grad[1] else None
-        return gs, gg
-
-
-_MBSTD_MASKS = {}
-
-
-def mbstd_tap_mask(extent, kernel, coef, device):
-    """coef * Mask, f32 [positions, taps] on `device`: Mask[pos, tap] = 1 where tap (kd, kh, kw order) of a SAME-padded
-    `kernel` convolution over `extent` = (d, h, w) reads inside the volume at output position pos.  Built on the host once per
-    (extent, kernel, coef, device) and kept: a captured step finds it ready."""
-    key = (tuple(int(e) for e in extent), tuple(int(k) for k in kernel), float(coef), str(device))
-    m = _MBSTD_MASKS.get(key)
-    if m is None:
-        axes = []
-        for e, k in zip(key[0], key[1]):
-            pos = torch.arange(e).reshape(e, 1) + torch.arange(k).reshape(1, k) - (k - 1) // 2
-            axes.append(((pos >= 0) & (pos < e)).to(torch.float32))                      # [extent, taps] of one axis
-        md, mh, mw = axes
-        full = md[:, None, None, :, None, None] * mh[None, :, None, None, :, None] * mw[None, None, :, None, None, :]
-        m = _MBSTD_MASKS[key] = (full.reshape(math.prod(key[0]), math.prod(key[1])) * float(coef)).to(device)
-    return m
-
-
-class _MbstdPlane(torch.autograd.Function):
-    """B[pos, :] = coef * sum over the taps in bounds at pos of w[tap, 0, :]: maskc [positions, taps] (mbstd_tap_mask) times
-    w [kd, kh, kw, 1, cout] as [taps, cout].  A few thousand products: torch element-wise ops (multiply, then a sum over the
-    taps, whose order is fixed).  The weight's gradient honours skip_param_grads and grads_into like a convolution's."""
-
-    @staticmethod
-    def forward(ctx, w, maskc):
-        ctx.save_for_backward(maskc)
-        ctx.w_shape, ctx.w_ptr = tuple(w.shape), w.data_ptr()
-        w2 = w.detach().reshape(maskc.shape[1], -1)
-        return (maskc.unsqueeze(-1) * w2.unsqueeze(0)).sum(dim=1)
-
-    @staticmethod
-    def backward(ctx, gB):
-        (maskc,) = ctx.saved_tensors
-        if not _wants(ctx, 0, ctx.w_ptr):
-            return None, None
-        prod = maskc.t().unsqueeze(-1) * gB.reshape(maskc.shape[0], -1).unsqueeze(0)      # [taps, positions, cout]
-        if torch.is_grad_enabled():
-            return prod.sum(dim=1).reshape(ctx.w_shape), None
-        out = _f32_out(ctx.w_ptr, ctx.w_shape, gB.device)
-        torch.sum(prod, dim=1, out=out.view(maskc.shape[1], -1))
-        return out, None
-
-
-def mbstd_stat(x, group, nseg=1):
-    """The minibatch-stddev statistic of x [N,C,D,H,W] as f32 [N] (networks/ops.py:313-325 without the concatenation): the batch
-    is `nseg` consecutive sub-batches, each grouped on its own (G = min(group, N / nseg), group m = samples g * M + m).  Twice
-    differentiable."""
-    return _MbstdStat.apply(x, int(group), int(nseg))
-
-
-def mbstd_plane(w, coef, extent):
-    """B f32 [D,H,W,cout] for mbstd_term from the statistic channel's filter w [kd,kh,kw,1,cout] and its runtime coefficient."""
-    if w.dim() != 5 or w.shape[3] != 1:
-        raise ValueError(f'mbstd_plane: expected a [kd, kh, kw, 1, cout] filter, got {tuple(w.shape)}')
-    B = _MbstdPlane.apply(w, mbstd_tap_mask(extent, w.shape[:3], coef, w.device)).reshape(*extent, w.shape[-1])
-    B._sg_w_ptr = w.data_ptr()
-    return B
-
-
-def mbstd_term(y, s, B):
-    """conv(concat(x, stat), W) = conv(x, W[..., :C, :]) + s (x) B: adds the statistic channel's share to y = the convolution of
-    the C real channels.  One f32 add per element, one rounding to y's type."""
-    return _MbstdTerm.apply(y, s, B, getattr(B, '_sg_w_ptr', 0), None, None)
-
-
-# ---- label conditioning (DESIGN.md 4.4): the generator's embedding concatenated to the latents, the discriminator's label-weighted
-# sum of its outputs.  Both are linear in everything that carries a gradient; the labels themselves are data.
-def _labels(c, n):
-    if c.dim() != 2 or c.shape[0] != n or not c.is_floating_point():
-        raise ValueError(f'conditioning: expected a floating [N, L] tensor with N = {n}, got {c.dtype} {tuple(c.shape)}')
-    return c.detach().contiguous().float()
-
-
-class _CondEmbed(torch.autograd.Function):
-    """out = concat([z, c @ W], 1) (sg_cond_embed): z [N, Z], c f32 [N, L], W f32 [L, Z] (a raw variable: no coefficient).  The
-    backward (the same entry point, adjoint = 1) writes dW straight into its slot of the flat gradient buffer (grads_into) and
-    honours skip_param_grads; nothing differentiates the generator's backward."""
-
-    @staticmethod
-    def forward(ctx, z, c, W):
-        _note_all(z)
-        lib = _lib.load()
-        _req_cuda(z, c, W)
-        n, zdim = z.shape
-        c = _labels(c, n)
-        if W.dim() != 2 or W.shape != (c.shape[1], zdim) or W.dtype != torch.float32:
-            raise ValueError(f'cond_embed: expected an f32 [{c.shape[1]}, {zdim}] embedding, got {W.dtype} {tuple(W.shape)}')
-        z = z.contiguous()
-        out = torch.empty((n, 2 * zdim), device=z.device, dtype=z.dtype)
-        check(lib.sg_cond_embed(_ptr(z), _ptr(c), _ptr(W.detach().contiguous()), _ptr(out), n, zdim, c.shape[1], 0, _dt(z),
-                                _stream()), 'sg_cond_embed')
-        ctx.save_for_backward(c)
-        ctx.w_ptr, ctx.w_shape = W.data_ptr(), tuple(W.shape)
-        return out
-
-    @staticmethod
-    @torch.autograd.function.once_differentiable
-    def backward(ctx, g):
-        lib = _lib.load()
-        (c,) = ctx.saved_tensors
-        want_z, want_w = ctx.needs_input_grad[0], _wants(ctx, 2, ctx.w_ptr)
-        if not (want_z or want_w):
-            return None, None, None
-        g = g.contiguous()
-        n, zdim = g.shape[0], g.shape[1] // 2
-        dz = torch.empty((n, zdim), device=g.device, dtype=g.dtype) if want_z else None
-        dW = _f32_out(ctx.w_ptr, ctx.w_shape, g.device) if want_w else None
-        check(lib.sg_cond_embed(_ptr(dz), _ptr(c), _ptr(dW), _ptr(g), n, zdim, c.shape[1], 1, _dt(g), _stream()),
-              'sg_cond_embed')
-        return dz, None, dW
-
-
-class _CondProject(torch.autograd.Function):
-    """adjoint False: out[n, 0] = sum_l o[n, l] * c[n, l]; adjoint True: out[n, l] = o[n, 0] * c[n, l] (sg_cond_project).  The two
-    are each other's backward, so the pair is differentiable to any order (the gradient penalty differentiates D's backward)."""
-
-    @staticmethod
-    def forward(ctx, o, c, adjoint):
-        _note_all(o)
-        lib = _lib.load()
-        _req_cuda(o, c)
-        c = _labels(c, o.shape[0])
-        n, l = c.shape
-        if o.dim() != 2 or o.shape[1] != (1 if adjoint else l):
-            raise ValueError(f'cond_project: labels {tuple(c.shape)} do not fit the tensor {tuple(o.shape)}')
-        o = o.contiguous()
-        out = torch.empty((n, l if adjoint else 1), device=o.device, dtype=o.dtype)
-        check(lib.sg_cond_project(_ptr(o), _ptr(c), _ptr(out), n, l, 1 if adjoint else 0, _dt(o), _stream()), 'sg_cond_project')
-        ctx.save_for_backward(c)
-        ctx.adjoint = adjoint
-        return out
-
-    @staticmethod
-    def backward(ctx, g):
-        (c,) = ctx.saved_tensors
-        return _CondProject.apply(g, c, not ctx.adjoint), None, None
-
-
-def cond_embed(z, c, W):
-    """concat([z, c @ W], axis=1) for latents z [N, Z], labels c [N, L] and the embedding W [L, Z] (SURFGAN_3D's
-    networks/surfgan/g_mapping.py:20-25): [N, 2 Z] of z's type, the product summed in f32."""
-    return _CondEmbed.apply(z, c, W)
-
-
-def cond_project(o, c):
-    """sum_l o[n, l] * c[n, l] as [N, 1] (networks/surfgan/discriminator.py:69) of o's type, summed in f32.  Twice differentiable
-    (and further) for o."""
-    return _CondProject.apply(o, c, False)
-
-
-def adam_step_size(lr, beta1, beta2, step):
-    """lr_t = lr * sqrt(1 - b2^t) / (1 - b1^t) (tf.train.AdamOptimizer), in host doubles."""
-    return lr * math.sqrt(1.0 - beta2 ** step) / (1.0 - beta1 ** step)
-
-
-def _dev_ptr(x):
-    """Device address of a one-element step scalar: a DevCoef, or a tensor (its first element)."""
-    return x.ptr() if isinstance(x, DevCoef) else _ptr(x)
-
-
-def adam_ema_(p, g, m, v, ema, lr, beta1, beta2, step, eps=1e-8, gscale=1.0, ema_decay=0.99, lr_dev=None, skip=None):
-    """In-place fused TF-Adam + EMA over flat f32 buffers.  lr_dev: a DevCoef (or one-element f32
-    device tensor) holding lr_t on the device (captured step): `lr` and `step` are then not used.  skip: a one-element int32
-    device flag (non-finite step guard, sg_adam_ema_guarded): set, the launch is the EMA-only update; clear, it computes
-    what the lr_dev launch computes.  Needs lr_dev."""
-    lib = _lib.load()
-    _req_cuda(p, g, m, v, ema)
-    if g is not None:
-        mark_packs_stale()   # the kernel rewrites parameters behind torch's version counters
-    if skip is not None:
-        if lr_dev is None or g is None:
-            raise ValueError('adam_ema_: a guarded launch needs the gradient and the step size on the device (lr_dev)')
-        check(lib.sg_adam_ema_guarded(_ptr(p), _ptr(g), _ptr(m), _ptr(v), _ptr(ema), p.numel(), _dev_ptr(lr_dev), _ptr(skip),
-                                      float(beta1), float(beta2), float(eps), float(gscale), float(ema_decay), _stream()),
-              'sg_adam_ema_guarded')
-        return
-    if lr_dev is not None and g is not None:
-        check(lib.sg_adam_ema_dev(_ptr(p), _ptr(g), _ptr(m), _ptr(v), _ptr(ema), p.numel(), _dev_ptr(lr_dev), float(beta1),
-                                  float(beta2), float(eps), float(gscale), float(ema_decay), _stream()), 'sg_adam_ema_dev')
-        return
-    lr_t = adam_step_size(lr, beta1, beta2, step) if g is not None else 0.0
-    check(lib.sg_adam_ema(_ptr(p), _ptr(g), _ptr(m), _ptr(v), _ptr(ema), p.numel(), float(lr_t), float(beta1),
-                          float(beta2), float(eps), float(gscale), float(ema_decay), _stream()), 'sg_adam_ema')
-
-
-def optim_step_(kind, p, g, s1, s2, ema, lr, h=0.0, eps=0.0, nesterov=False, gscale=1.0, ema_decay=0.99, lr_dev=None,
-                skip=None):
-    """In-place fused SGD / Momentum / Adadelta (+ EMA) over flat f32 buffers (sg_optim_step; lr_dev: the learning rate as
-    a DevCoef or one-element f32 tensor on the device, captured step; skip: the guard's int32 device flag, as in adam_ema_)."""
-    lib = _lib.load()
-    _req_cuda(p, g, s1, s2, ema)
-    mark_packs_stale()      # the kernel rewrites parameters behind torch's version counters
-    if skip is not None:
-        if lr_dev is None:
-            raise ValueError('optim_step_: a guarded launch needs the step size on the device (lr_dev)')
-        check(lib.sg_optim_step_guarded(int(kind), _ptr(p), _ptr(g), _ptr(s1), _ptr(s2), _ptr(ema), p.numel(), _dev_ptr(lr_dev),
-                                        _ptr(skip), float(h), float(eps), 1 if nesterov else 0, float(gscale),
-                                        float(ema_decay), _stream()), 'sg_optim_step_guarded')
-        return
-    if lr_dev is not None:
-        check(lib.sg_optim_step_dev(int(kind), _ptr(p), _ptr(g), _ptr(s1), _ptr(s2), _ptr(ema), p.numel(), _dev_ptr(lr_dev), float(h),
-                                    float(eps), 1 if nesterov else 0, float(gscale), float(ema_decay), _stream()),
-              'sg_optim_step_dev')
-        return
-    check(lib.sg_optim_step(int(kind), _ptr(p), _ptr(g), _ptr(s1), _ptr(s2), _ptr(ema), p.numel(), float(lr), float(h),
-                            float(eps), 1 if nesterov else 0, float(gscale), float(ema_decay), _stream()),
-          'sg_optim_step')
-
-
-def segment_table_arrays(segments, total, chunk=_lib.SG_SEG_CHUNK):
-    """Host half of SegmentTable: segments [(start, count, decay flag)] of a flat buffer of `total` elements ->
-    (segs [[start, count, flag, first block]], blocks [[segment, chunk]]) as include/saragan_hip.h lays them out."""
-    segs, blocks, end = [], [], 0
-    for s, (start, count, flag) in enumerate(sorted((int(a), int(b), int(bool(c))) for a, b, c in segments)):
-        if start % 4 or count < 1 or start < end or start + count > total:
-            raise ValueError(f'segment [{start}, {start + count}) of a flat buffer of {total}: starts must be multiples of 4 and '
-                             f'segments disjoint and inside the buffer')
-        end = start + count
-        segs.append([start, count, flag, len(blocks)])
-        blocks.extend([s, c] for c in range((count + chunk - 1) // chunk))
-    if not segs:
-        raise ValueError('a segment table needs at least one segment')
-    return segs, blocks
-
-
-class SegmentTable:
-    """Device table of a train op's variables for the segmented optimiser launches (sg_adamw_ema, sg_lamb_*), with LAMB's
-    workspace: per-block partial sums and per-segment trust ratios.  Built once per train op (it copies to the device);
-    a step only launches with it."""
-
-    def __init__(self, segments, total, device):
-        segs, blocks = segment_table_arrays(segments, total)
-        self.total, self.nseg, self.nblocks = int(total), len(segs), len(blocks)
-        self.segs = torch.tensor(segs, dtype=torch.int64).to(device)
-        self.blocks = torch.tensor(blocks, dtype=torch.int32).to(device)
-        self.partials = torch.zeros(2 * self.nblocks, dtype=torch.float32, device=device)
-        self.ratios = torch.ones(self.nseg, dtype=torch.float32, device=device)
-
-    def check(self, *bufs):
-        _req_cuda(*bufs)
-        for b in bufs:
-            if b is not None and (b.dtype != torch.float32 or not b.is_contiguous() or b.numel() != self.total):
-                raise ValueError(f'the segment table describes contiguous float32 buffers of {self.total} elements')
-
-
-def adamw_ema_(table, p, g, m, v, ema, lr, beta1, beta2, eps=1e-6, decay=0.0, gscale=1.0, ema_decay=0.99, lr_dev=None,
-               skip=None):
-    """In-place AdamW (no bias correction; decay on the table's flagged segments) + EMA over the segments of whole flat f32
-    buffers: ONE launch (sg_adamw_ema).  lr_dev / skip as in adam_ema_."""
-    lib = _lib.load()
-    table.check(p, g, m, v, ema)
-    if skip is not None and lr_dev is None:
-        raise ValueError('adamw_ema_: a guarded launch needs the step size on the device (lr_dev)')
-    mark_packs_stale()      # the kernel rewrites parameters behind torch's version counters
-    check(lib.sg_adamw_ema(_ptr(p), _ptr(g), _ptr(m), _ptr(v), _ptr(ema), table.total, _ptr(table.segs), _ptr(table.blocks),
-                           table.nseg, table.nblocks, float(lr), None if lr_dev is None else _dev_ptr(lr_dev), _ptr(skip),
-                           float(beta1), float(beta2), float(eps), float(decay), float(gscale), float(ema_decay), _stream()),
-          'sg_adamw_ema')
-
-
-def lamb_ema_(table, p, g, m, v, ema, t, lr, beta1, beta2, eps=1e-6, decay=0.0, gscale=1.0, ema_decay=0.99, lr_dev=None,
-              skip=None):
-    """In-place LAMB + EMA over the segments of whole flat f32 buffers: moments and per-block norms (sg_lamb_moments), one
-    trust ratio per segment (sg_lamb_ratios), update (sg_lamb_update) -- three launches whatever the number of segments.
-    t: the int64 [1] device count of applied updates.  Unguarded, the launches advance it; with skip (the guard's flag;
-    needs lr_dev) sg_guard_step has advanced it already, and a set flag leaves everything but the EMA as it was."""
-    lib = _lib.load()
-    table.check(p, g, m, v, ema)
-    _req_cuda(t)
-    if t.dtype != torch.int64:
-        raise TypeError('lamb_ema_: the step count is an int64 device tensor')
-    if skip is not None and lr_dev is None:
-        raise ValueError('lamb_ema_: a guarded launch needs the step size on the device (lr_dev)')
-    mark_packs_stale()      # the kernels rewrite parameters behind torch's version counters
-    advance = 0 if skip is not None else 1
-    tab = (_ptr(table.segs), _ptr(table.blocks), table.nseg, table.nblocks)
-    check(lib.sg_lamb_moments(_ptr(p), _ptr(g), _ptr(m), _ptr(v), table.total, *tab, _ptr(table.partials), _ptr(t), advance,
-                              _ptr(skip), float(beta1), float(beta2), float(eps), float(decay), float(gscale), _stream()),
-          'sg_lamb_moments')
-    check(lib.sg_lamb_ratios(_ptr(table.segs), table.nseg, table.nblocks, _ptr(table.partials), _ptr(table.ratios), _ptr(t),
-                             advance, _ptr(skip), _stream()), 'sg_lamb_ratios')
-    check(lib.sg_lamb_update(_ptr(p), _ptr(m), _ptr(v), _ptr(ema), table.total, *tab, _ptr(table.ratios), _ptr(t), float(lr),
-                             None if lr_dev is None else _dev_ptr(lr_dev), _ptr(skip), float(beta1), float(beta2), float(eps),
-                             float(decay), float(ema_decay), _stream()), 'sg_lamb_update')
-
-
-SPECTRAL_MIN_ROWS = 16      # fewest rows of a row block (where the layer has that many): bounds the column workspace at 1/16 of W
-SPECTRAL_MAX_BLOCKS = 128   # most row blocks of one layer (while a block stays within `chunk` rows): the layer's ONE normalising
-#                             block adds that many partials per column, and the longest such chain bounds the launch
-
-
-def spectral_rows_per_block(rows, cols, chunk=_lib.SG_SEG_CHUNK):
-    """Rows of one row block of an [rows, cols] weight: about `chunk` elements, whole rows only, at least SPECTRAL_MIN_ROWS and
-    at least rows / SPECTRAL_MAX_BLOCKS (a large layer's blocks loop), never more than `chunk` rows (the kernel's copy of t)
-    or than the layer has."""
-    rows, cols = int(rows), int(cols)
-    want = max(chunk // cols, SPECTRAL_MIN_ROWS, -(-rows // SPECTRAL_MAX_BLOCKS))
-    return max(1, min(rows, chunk, want))
-
-
-def spectral_table_arrays(segments, total, chunk=_lib.SG_SEG_CHUNK):
-    """Host half of SpectralTable: segments [(start, R, C)] of a flat buffer of `total` elements -> (segs [[start, R, C, first
-    block, rows per block, u offset, v offset, column offset]], blocks [[segment, row block]], ulen, vlen, collen) as
-    include/saragan_hip.h lays them out.  u, v and the column partials of the segments follow each other, each start rounded
-    up to a multiple of 4."""
-    segs, blocks, end, uoff, voff, coloff = [], [], 0, 0, 0, 0
-    pad = lambda n: (n + 3) // 4 * 4
-    for s, (start, rows, cols) in enumerate(sorted((int(a), int(b), int(c)) for a, b, c in segments)):
-        if start % 4 or rows < 1 or cols < 1 or start < end or start + rows * cols > total:
-            raise ValueError(f'segment [{start}, {start + rows * cols}) of a flat buffer of {total}: starts must be multiples '
-                             f'of 4 and segments disjoint and inside the buffer')
-        end = start + rows * cols
-        rpb = spectral_rows_per_block(rows, cols, chunk)
-        nb = (rows + rpb - 1) // rpb
-        segs.append([start, rows, cols, len(blocks), rpb, uoff, voff, coloff])
-        blocks.extend([s, b] for b in range(nb))
-        uoff, voff, coloff = uoff + pad(cols), voff + pad(rows), coloff + pad(nb * cols)
-    if not segs:
-        raise ValueError('a spectral table needs at least one segment')
-    return segs, blocks, uoff, voff, coloff
-
-
-class SpectralTable:
-    """Device table of one network's spectrally normalised weights (sg_spectral_*) with their state and workspaces: u (the
-    persistent power-iteration vectors, all layers in one buffer), v, sigma, and the partial sums.  Built once per flat
-    buffer (it copies to the device); a step only launches with it."""
-
-    def __init__(self, segments, total, device):
-        segs, blocks, ulen, vlen, collen = spectral_table_arrays(segments, total)
-        self.total, self.nseg, self.nblocks = int(total), len(segs), len(blocks)
-        self.ulen, self.vlen, self.collen = ulen, vlen, collen
-        self.layout = segs
-        self.segs = torch.tensor(segs, dtype=torch.int64).to(device)
-        self.blocks = torch.tensor(blocks, dtype=torch.int32).to(device)
-        z = lambda n: torch.zeros(n, dtype=torch.float32, device=device)
-        self.u, self.v, self.cols = z(ulen), z(vlen), z(collen)
-        self.sigma, self.nt, self.partials = z(self.nseg), z(self.nseg), z(self.nblocks)
-
-    def check(self, *bufs):
-        _req_cuda(*bufs)
-        for b in bufs:
-            if b.dtype != torch.float32 or not b.is_contiguous() or b.numel() != self.total:
-                raise ValueError(f'the spectral table describes contiguous float32 buffers of {self.total} elements')
-
-    def views(self, s):
-        """(u [1, C], v [1, R], sigma [1]) of segment s: views of the table's buffers."""
-        _, rows, cols, _, _, uo, vo, _ = self.layout[s]
-        return self.u[uo:uo + cols].view(1, cols), self.v[vo:vo + rows].view(1, rows), self.sigma[s:s + 1]
-
-
-def spectral_refresh_(table, p, eff, iteration=1):
-    """One power-iteration refresh of every normalised weight of the flat f32 parameter buffer p: updates table.u, writes
-    table.v, table.sigma and W / sigma into the flat effective-weight buffer eff (same offsets) -- 2 * iteration + 1 launches
-    whatever the number of layers (sg_spectral_refresh)."""
-    lib = _lib.load()
-    table.check(p, eff)
-    if int(iteration) < 1:
-        raise ValueError('spectral_refresh_: iteration >= 1')
-    if p.data_ptr() == eff.data_ptr():
-        raise ValueError('spectral_refresh_: the effective weights need a buffer of their own')
-    mark_packs_stale()      # the kernel rewrites the effective weights behind torch's version counters
-    check(lib.sg_spectral_refresh(_ptr(p), _ptr(eff), table.total, _ptr(table.segs), _ptr(table.blocks), table.nseg,
-                                  table.nblocks, _ptr(table.u), table.ulen, _ptr(table.v), table.vlen, _ptr(table.sigma),
-                                  _ptr(table.nt), _ptr(table.partials), _ptr(table.cols), table.collen, int(iteration),
-                                  _stream()), 'sg_spectral_refresh')
-
-
-def spectral_pullback_(table, g, eff):
-    """In place on the flat gradient buffer: the gradient with respect to the effective weights becomes the one with respect to
-    the raw weights, g = (g - <g, W / sigma> v^T u) / sigma per normalised layer with u, v constant -- two launches
-    (sg_spectral_pullback).  Elements outside the table's segments keep their bits."""
-    lib = _lib.load()
-    table.check(g, eff)
-    check(lib.sg_spectral_pullback(_ptr(g), _ptr(eff), table.total, _ptr(table.segs), _ptr(table.blocks), table.nseg,
-                                   table.nblocks, _ptr(table.u), table.ulen, _ptr(table.v), table.vlen, _ptr(table.sigma),
-                                   _ptr(table.partials), _stream()), 'sg_spectral_pullback')
-
-
-def segment_sumsq(flat, offsets_dev, nseg, flag=None, accumulate=False):
-    """Per-segment sums of squares; flag (a one-element int32 device tensor): also the all-finite test of nonfinite_flag_
-    on the values read (sg_segment_sumsq_flag)."""
-    lib = _lib.load()
-    out = torch.empty(nseg, device=flat.device, dtype=torch.float32)
-    if flag is not None:
-        check(lib.sg_segment_sumsq_flag(_ptr(flat), _ptr(offsets_dev), _ptr(out), nseg, _ptr(flag), 1 if accumulate else 0,
-                                        _stream()), 'sg_segment_sumsq_flag')
-        return out
-    check(lib.sg_segment_sumsq(_ptr(flat), _ptr(offsets_dev), _ptr(out), nseg, _stream()), 'sg_segment_sumsq')
-    return out
-
-
-def nonfinite_flag_(flag, x, accumulate=False):
-    """flag (one-element int32 device tensor) = 1 if any entry of the flat f32 tensor x is NaN or +-Inf, else 0
-    (sg_nonfinite_flag; accumulate=True ORs into the flag instead of clearing it first).  No host sync."""
-    lib = _lib.load()
-    _req_cuda(flag, x)
-    if flag.dtype != torch.int32 or x.dtype != torch.float32 or not x.is_contiguous():
-        raise TypeError('nonfinite_flag_: an int32 flag and a contiguous float32 buffer')
-    check(lib.sg_nonfinite_flag(_ptr(x), x.numel(), _ptr(flag), 1 if accumulate else 0, _stream()), 'sg_nonfinite_flag')
-    return flag
-
-
-def guard_step_(flag, t, counters, lr, lr_t, adam=None, lr_dev=None):
-    """Bookkeeping of a guarded train op (sg_guard_step, one thread): flag clear -> t += 1 and lr_t = the step size at the
-    new t (adam=(beta1, beta2): Adam's bias-corrected lr, in double as adam_step_size; None: lr); flag set -> counters
-    [skipped, consecutive, longest run] advance.  t: int64 [1], counters: int64 [3], lr_t: f32 [1] (device tensors);
-    lr_dev: a float64 DevCoef read instead of `lr` (captured step)."""
-    lib = _lib.load()
-    _req_cuda(flag, t, counters, lr_t)
-    b1, b2 = adam if adam is not None else (0.0, 0.0)
-    check(lib.sg_guard_step(_ptr(flag), _ptr(t), _ptr(counters), float(lr), None if lr_dev is None else _dev_ptr(lr_dev),
-                            _ptr(lr_t), 1 if adam is not None else 0, float(b1), float(b2), _stream()), 'sg_guard_step')
-
-
-# ---- batches from a resident table (DESIGN.md 4.6; dataset.ResidentLoader): out[i] = f32(table[idx[i]]), optionally normalised
-_SRC_DT = {torch.uint8: _lib.SG_SRC_U8, torch.int8: _lib.SG_SRC_I8, torch.int16: _lib.SG_SRC_I16, torch.uint16: _lib.SG_SRC_U16,
-           torch.float16: _lib.SG_SRC_F16, torch.float32: _lib.SG_SRC_F32}
-
-
-def check_positions(positions, rows):
-    """Host table positions as a contiguous int32 array; ValueError if one lies outside [0, rows).  (The kernel guards itself
-    as well -- such a row comes back as NaN -- but a bad draw is a bug of the caller's and is reported where it is made.)"""
-    import numpy as np
-    pos = np.ascontiguousarray(positions.numpy() if torch.is_tensor(positions) else positions)
-    if pos.ndim != 1 or (pos.size and not np.issubdtype(pos.dtype, np.integer)):
-        raise ValueError(f'gather_rows: expected a 1-D sequence of integer positions, got {pos.dtype} {pos.shape}')
-    if pos.size and (int(pos.min()) < 0 or int(pos.max()) >= rows):
-        bad = int(pos[(pos < 0) | (pos >= rows)][0])
-        raise ValueError(f'gather_rows: position {bad} lies outside the table of {rows} rows')
-    return pos.astype(np.int32, copy=False)
-
-
-def gather_rows(table, idx, mean=None, stddev=None, out=None):
-    """f32 [n, ...] = the rows idx of table [rows, ...] (u8 / i8 / i16 / u16 / f16 / f32), converted exactly and, with mean and
-    stddev, normalised as (x - mean) / stddev in two correctly rounded f32 operations: the bits np.subtract / np.divide with
-    np.float32 scalars give (sg_gather_rows, one launch).  idx: host positions (a sequence, an array or a CPU tensor: validated,
-    then uploaded) or an int32 tensor on the table's device (used as it is: a position outside the table gives a NaN row).
-    out: an f32 buffer of the result's shape to write into.  A CPU table takes the same two numpy operations in the same order."""
-    if (mean is None) != (stddev is None):
-        raise ValueError('gather_rows: give both mean and stddev, or neither')
-    if table.dtype not in _SRC_DT:
-        raise TypeError(f'gather_rows: tables are uint8, int8, int16, uint16, float16 or float32, got {table.dtype}')
-    if table.dim() < 1 or not table.is_contiguous():
-        raise ValueError('gather_rows: expected a contiguous [rows, ...] table')
-    rows = table.shape[0]
-    on_device = torch.is_tensor(idx) and idx.is_cuda
-    if on_device:
-        if not table.is_cuda or idx.device != table.device or idx.dtype != torch.int32 or idx.dim() != 1 or not idx.is_contiguous():
-            raise ValueError('gather_rows: device positions are a contiguous 1-D int32 tensor on the table\'s device')
-    else:
-        pos = check_positions(idx, rows)
-    n = idx.shape[0] if on_device else pos.shape[0]
-    shape = (n,) + tuple(table.shape[1:])
-    if out is not None and (tuple(out.shape) != shape or out.dtype != torch.float32 or out.device != table.device
-                            or not out.is_contiguous()):
-        raise ValueError(f'gather_rows: out must be a contiguous float32 {shape} tensor on {table.device}')
-    if not table.is_cuda:
-        import numpy as np
-        res = np.empty(shape, dtype=np.float32)
-        np.copyto(res, table.numpy()[pos], casting='unsafe')
-        if mean is not None:
-            np.subtract(res, np.float32(mean), out=res)
-            np.divide(res, np.float32(stddev), out=res)
-        res = torch.from_numpy(res)
-        return res if out is None else out.copy_(res)
-    lib = _lib.load()
-    if not on_device:
-        idx = torch.from_numpy(pos).to(table.device)
-    if out is None:
-        out = torch.empty(shape, device=table.device, dtype=torch.float32)
-    row_elems = table.numel() // rows if rows else max(1, math.prod(table.shape[1:]))
-    check(lib.sg_gather_rows(_ptr(table), _SRC_DT[table.dtype], rows, row_elems, _ptr(idx), n, _ptr(out),
-                             0 if mean is None else 1, 0.0 if mean is None else float(mean), 1.0 if mean is None else float(stddev),
-                             _stream()), 'sg_gather_rows')
-    return out
-
-
-# ---- voxel-intensity histograms (DESIGN.md 4.7; metrics/intensity_metrics.py) ---------------------------------------------------
-_HIST_DT = dict(_SRC_DT)
-_HIST_DT[torch.bfloat16] = _lib.SG_SRC_BF16
-
-
-def intensity_hist(x, lo, hi, scale=1.0, shift=0.0, pooled=False, out=None, accumulate=False):
-    """int64 [rows, hi - lo + 1] counts of x [n, ...] (u8 / i8 / i16 / u16 / f16 / bf16 / f32, contiguous, on the device) in the
-    unit-wide bins of [lo, hi] after t = x * scale + shift, two correctly rounded f32 operations (sg_intensity_hist, one
-    launch): column min(floor(t) - lo, hi - lo - 1), values under lo in the first bin and values from hi on in the last (the top
-    edge is closed), NaN in the extra last column -- so every row sums to its element count.  pooled=False: one row per
-    sample; pooled=True: one row for the whole batch.  out: an int64 buffer of the result's shape; accumulate=True adds to it
-    instead of overwriting it."""
-    if not torch.is_tensor(x):
-        raise TypeError(f'intensity_hist: expected a tensor, got {type(x).__name__}')
-    if x.dtype not in _HIST_DT:
-        raise TypeError(f'intensity_hist: inputs are uint8, int8, int16, uint16, float16, bfloat16 or float32, got {x.dtype}')
-    if x.dim() < 1 or not x.is_contiguous():
-        raise ValueError('intensity_hist: expected a contiguous [n, ...] tensor')
-    lo, hi = int(lo), int(hi)
-    if hi <= lo:
-        raise ValueError(f'intensity_hist: the range [{lo}, {hi}] is empty')
-    bins = hi - lo
-    if bins > _lib.INTENSITY_HIST_MAX_BINS:
-        raise ValueError(f'intensity_hist: {bins} bins, at most {_lib.INTENSITY_HIST_MAX_BINS} fit the kernel\'s LDS image')
-    if lo < -2 ** 31 or hi > 2147483520:      # (the largest int32 a float32 holds)
-        raise ValueError(f'intensity_hist: the range [{lo}, {hi}] does not fit 32-bit integers that float32 can bound')
-    if not math.isfinite(float(scale)):
-        raise ValueError(f'intensity_hist: scale {scale} is not finite')
-    n = x.shape[0]
-    rows, row_elems = (1, x.numel()) if pooled else (n, x.numel() // n if n else math.prod(x.shape[1:]))
-    shape = (rows, bins + 1)
-    if out is None:
-        if accumulate:
-            raise ValueError('intensity_hist: accumulate=True needs the buffer to add to (out)')
-    elif (not torch.is_tensor(out) or tuple(out.shape) != shape or out.dtype != torch.int64 or out.device != x.device
-          or not out.is_contiguous()):
-        raise ValueError(f'intensity_hist: out must be a contiguous int64 {shape} tensor on {x.device}')
-    if not x.is_cuda:
-        raise ValueError('intensity_hist: the input is a device tensor (there is no CPU path)')
-    lib = _lib.load()
-    if out is None:
-        out = torch.empty(shape, device=x.device, dtype=torch.int64)
-    with torch.cuda.device(x.device):
-        check(lib.sg_intensity_hist(_ptr(x), _HIST_DT[x.dtype], rows, row_elems, float(scale), float(shift), lo, bins, _ptr(out),
-                                    1 if accumulate else 0, _stream()), 'sg_intensity_hist')
-    return out

@@ -19,6 +19,7 @@ import numpy as np
 import torch
 
 from .. import functional as F
+from ..table_ops import HIST_DT
 from . import swd as SWD
 
 
@@ -110,7 +111,7 @@ class IntensityAccumulator:
     def _add_side(self, x, buf, keep):
         if not torch.is_tensor(x) or not x.is_cuda:
             raise RuntimeError('saragan_amd.metrics run on the GPU only (no CPU fallback)')
-        if x.dtype not in F._HIST_DT:
+        if x.dtype not in HIST_DT:
             x = x.to(torch.float32)
         x = x.contiguous()
         F.intensity_hist(x, self.lo, self.hi, self.scale, self.shift, pooled=True, out=self._row(buf, 0), accumulate=True)

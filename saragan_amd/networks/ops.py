@@ -10,6 +10,7 @@ import os
 import numpy as np
 import torch
 
+from .. import _lib
 from .. import functional as F
 from ..varstore import compute_dtype, get_variable, variable_scope  # noqa: F401  (re-exported)
 
@@ -409,7 +410,7 @@ def avg_pool3d(x, factor=2, gain=1):
         # activation is never written (functional._ConvBiasActPool)
         try:
             return F.conv3d_act_pool(x.x, x.w, x.coef, x.bias, x.slope, x.in_info)
-        except F._lib.SgError:
+        except _lib.SgError:
             pass
     x, in_info = _consume(x, premask=True)     # its gradient (an up-scale) can carry the producer's LeakyReLU mask
     return F.downscale2x(x, float(gain) / 8.0, in_info)

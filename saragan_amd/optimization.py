@@ -18,6 +18,7 @@ import os
 import numpy as np
 import torch
 
+from . import _lib
 from . import functional as F
 from . import step_capture as SC
 from .networks.loss import forward_discriminator, forward_generator, forward_simultaneous, linear_generator_link
@@ -129,13 +130,13 @@ class _FusedRule(_Optimizer):
 
 class GradientDescentOptimizer(_FusedRule):
     """tf.train.GradientDescentOptimizer(learning_rate): p -= lr * g (optimization.py:17-18,29-30)."""
-    KIND = F._lib.SG_OPT_SGD
+    KIND = _lib.SG_OPT_SGD
 
 
 class MomentumOptimizer(_FusedRule):
     """tf.train.MomentumOptimizer(learning_rate, momentum, use_nesterov): accum = momentum * accum + g;
     p -= lr * g + lr * momentum * accum (Nesterov, what optimization.py:21-22,34-35 asks for) or lr * accum."""
-    KIND, SLOTS = F._lib.SG_OPT_MOMENTUM, ('accum',)
+    KIND, SLOTS = _lib.SG_OPT_MOMENTUM, ('accum',)
 
     def __init__(self, learning_rate, momentum, use_nesterov=False):
         super().__init__(learning_rate)
@@ -147,7 +148,7 @@ class MomentumOptimizer(_FusedRule):
 
 class AdadeltaOptimizer(_FusedRule):
     """tf.train.AdadeltaOptimizer(learning_rate, rho, epsilon) (optimization.py:19-20,31-32: epsilon 1e-07)."""
-    KIND, SLOTS = F._lib.SG_OPT_ADADELTA, ('accum', 'accum_update')
+    KIND, SLOTS = _lib.SG_OPT_ADADELTA, ('accum', 'accum_update')
 
     def __init__(self, learning_rate, rho=0.95, epsilon=1e-8):
         super().__init__(learning_rate)

@@ -5,6 +5,7 @@ import time
 
 import torch
 
+from . import _lib
 from . import functional as F
 from .networks import loss as L
 from .varstore import compute_dtype
@@ -38,7 +39,7 @@ def capturable(sg, train_ids, real):
         return False                         # the full training step only
     if any(type(sg.trains[t]['optimizer'].distributed).__name__ == 'AdasumReducer' for t in train_ids):
         return False                         # Adasum combines weight deltas around the optimiser step: eager
-    if F._lib.load().sg_prof_enabled():
+    if _lib.load().sg_prof_enabled():
         return False                         # the profiler brackets launches with events: never inside a capture
     return L.graph_safe(L._rng(real.device))
 

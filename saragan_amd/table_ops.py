@@ -1,0 +1,119 @@
+"""Reads of typed device tables: batches gathered from a resident dataset (dataset.ResidentLoader) and
+voxel-intensity histograms (metrics/intensity_metrics.py).  Re-exported by functional."""
+import math
+
+import torch
+
+from . import _lib
+from ._launch import _ptr, _stream
+from ._lib import check
+
+# ---- batches from a resident table: out[i] = f32(table[idx[i]]), optionally normalised
+SRC_DT = {torch.uint8: _lib.SG_SRC_U8, torch.int8: _lib.SG_SRC_I8, torch.int16: _lib.SG_SRC_I16, torch.uint16: _lib.SG_SRC_U16,
+          torch.float16: _lib.SG_SRC_F16, torch.float32: _lib.SG_SRC_F32}
+
+
+def check_positions(positions, rows):
+    """Host table positions as a contiguous int32 array; ValueError if one lies outside [0, rows).  (The kernel guards itself
+    as well -- such a row comes back as NaN -- but a bad draw is a bug of the caller's and is reported where it is made.)"""
+    import numpy as np
+    pos = np.ascontiguousarray(positions.numpy() if torch.is_tensor(positions) else positions)
+    if pos.ndim != 1 or (pos.size and not np.issubdtype(pos.dtype, np.integer)):
+        raise ValueError(f'gather_rows: expected a 1-D sequence of integer positions, got {pos.dtype} {pos.shape}')
+    if pos.size and (int(pos.min()) < 0 or int(pos.max()) >= rows):
+        bad = int(pos[(pos < 0) | (pos >= rows)][0])
+        raise ValueError(f'gather_rows: position {bad} lies outside the table of {rows} rows')
+    return pos.astype(np.int32, copy=False)
+
+
+def gather_rows(table, idx, mean=None, stddev=None, out=None):
+    """f32 [n, ...] = the rows idx of table [rows, ...] (u8 / i8 / i16 / u16 / f16 / f32), converted exactly and, with mean and
+    stddev, normalised as (x - mean) / stddev in two correctly rounded f32 operations: the bits np.subtract / np.divide with
+    np.float32 scalars give (sg_gather_rows, one launch).  idx: host positions (a sequence, an array or a CPU tensor: validated,
+    then uploaded) or an int32 tensor on the table's device (used as it is: a position outside the table gives a NaN row).
+    out: an f32 buffer of the result's shape to write into.  A CPU table takes the same two numpy operations in the same order."""
+    if (mean is None) != (stddev is None):
+        raise ValueError('gather_rows: give both mean and stddev, or neither')
+    if table.dtype not in SRC_DT:
+        raise TypeError(f'gather_rows: tables are uint8, int8, int16, uint16, float16 or float32, got {table.dtype}')
+    if table.dim() < 1 or not table.is_contiguous():
+        raise ValueError('gather_rows: expected a contiguous [rows, ...] table')
+    rows = table.shape[0]
+    on_device = torch.is_tensor(idx) and idx.is_cuda
+    if on_device:
+        if not table.is_cuda or idx.device != table.device or idx.dtype != torch.int32 or idx.dim() != 1 or not idx.is_contiguous():
+            raise ValueError('gather_rows: device positions are a contiguous 1-D int32 tensor on the table\'s device')
+    else:
+        pos = check_positions(idx, rows)
+    n = idx.shape[0] if on_device else pos.shape[0]
+    shape = (n,) + tuple(table.shape[1:])
+    if out is not None and (tuple(out.shape) != shape or out.dtype != torch.float32 or out.device != table.device
+                            or not out.is_contiguous()):
+        raise ValueError(f'gather_rows: out must be a contiguous float32 {shape} tensor on {table.device}')
+    if not table.is_cuda:
+        import numpy as np
+        res = np.empty(shape, dtype=np.float32)
+        np.copyto(res, table.numpy()[pos], casting='unsafe')
+        if mean is not None:
+            np.subtract(res, np.float32(mean), out=res)
+            np.divide(res, np.float32(stddev), out=res)
+        res = torch.from_numpy(res)
+        return res if out is None else out.copy_(res)
+    lib = _lib.load()
+    if not on_device:
+        idx = torch.from_numpy(pos).to(table.device)
+    if out is None:
+        out = torch.empty(shape, device=table.device, dtype=torch.float32)
+    row_elems = table.numel() // rows if rows else max(1, math.prod(table.shape[1:]))
+    check(lib.sg_gather_rows(_ptr(table), SRC_DT[table.dtype], rows, row_elems, _ptr(idx), n, _ptr(out),
+                             0 if mean is None else 1, 0.0 if mean is None else float(mean), 1.0 if mean is None else float(stddev),
+                             _stream()), 'sg_gather_rows')
+    return out
+
+
+# ---- voxel-intensity histograms
+HIST_DT = dict(SRC_DT)
+HIST_DT[torch.bfloat16] = _lib.SG_SRC_BF16
+
+
+def intensity_hist(x, lo, hi, scale=1.0, shift=0.0, pooled=False, out=None, accumulate=False):
+    """int64 [rows, hi - lo + 1] counts of x [n, ...] (u8 / i8 / i16 / u16 / f16 / bf16 / f32, contiguous, on the device) in the
+    unit-wide bins of [lo, hi] after t = x * scale + shift, two correctly rounded f32 operations (sg_intensity_hist, one
+    launch): column min(floor(t) - lo, hi - lo - 1), values under lo in the first bin and values from hi on in the last (the top
+    edge is closed), NaN in the extra last column -- so every row sums to its element count.  pooled=False: one row per
+    sample; pooled=True: one row for the whole batch.  out: an int64 buffer of the result's shape; accumulate=True adds to it
+    instead of overwriting it."""
+    if not torch.is_tensor(x):
+        raise TypeError(f'intensity_hist: expected a tensor, got {type(x).__name__}')
+    if x.dtype not in HIST_DT:
+        raise TypeError(f'intensity_hist: inputs are uint8, int8, int16, uint16, float16, bfloat16 or float32, got {x.dtype}')
+    if x.dim() < 1 or not x.is_contiguous():
+        raise ValueError('intensity_hist: expected a contiguous [n, ...] tensor')
+    lo, hi = int(lo), int(hi)
+    if hi <= lo:
+        raise ValueError(f'intensity_hist: the range [{lo}, {hi}] is empty')
+    bins = hi - lo
+    if bins > _lib.INTENSITY_HIST_MAX_BINS:
+        raise ValueError(f'intensity_hist: {bins} bins, at most {_lib.INTENSITY_HIST_MAX_BINS} fit the kernel\'s LDS image')
+    if lo < -2 ** 31 or hi > 2147483520:      # (the largest int32 a float32 holds)
+        raise ValueError(f'intensity_hist: the range [{lo}, {hi}] does not fit 32-bit integers that float32 can bound')
+    if not math.isfinite(float(scale)):
+        raise ValueError(f'intensity_hist: scale {scale} is not finite')
+    n = x.shape[0]
+    rows, row_elems = (1, x.numel()) if pooled else (n, x.numel() // n if n else math.prod(x.shape[1:]))
+    shape = (rows, bins + 1)
+    if out is None:
+        if accumulate:
+            raise ValueError('intensity_hist: accumulate=True needs the buffer to add to (out)')
+    elif (not torch.is_tensor(out) or tuple(out.shape) != shape or out.dtype != torch.int64 or out.device != x.device
+          or not out.is_contiguous()):
+        raise ValueError(f'intensity_hist: out must be a contiguous int64 {shape} tensor on {x.device}')
+    if not x.is_cuda:
+        raise ValueError('intensity_hist: the input is a device tensor (there is no CPU path)')
+    lib = _lib.load()
+    if out is None:
+        out = torch.empty(shape, device=x.device, dtype=torch.int64)
+    with torch.cuda.device(x.device):
+        check(lib.sg_intensity_hist(_ptr(x), HIST_DT[x.dtype], rows, row_elems, float(scale), float(shift), lo, bins, _ptr(out),
+                                    1 if accumulate else 0, _stream()), 'sg_intensity_hist')
+    return out

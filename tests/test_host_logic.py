@@ -404,15 +404,18 @@ def test_mixed_in_place_and_out_of_place_contributions_are_refused():
 def test_packed_image_cache_states():
     """functional.mark_packs_stale / clear_pack_cache (host logic only)."""
     from saragan_amd import functional as F
+    from saragan_amd import _weight_images as WI
+    images = F.IMAGES
     F.clear_pack_cache()
     F.mark_packs_stale()
-    assert F._PACK_STATE['stale'] is False          # nothing cached: nothing to refresh
-    F._PACK_CACHE[('rgbmat', 1)] = (object(), object())
-    F._PACK_CACHE[(123, 0, 1.0, False, 1, 8, 8, 3, 3, 3)] = (object(), object(), object(), object())
+    assert images.stale is False          # nothing cached: nothing to refresh
+    rgb = WI.ImageKey(WI.RGB_MATRIX, 1, 0, 1.0, False, None, 8, 1, 1, 1, 1)
+    images._entries[rgb] = WI.ImageEntry(object(), object(), None)
+    images._entries[WI.ImageKey(WI.FRAGMENT, 123, 0, 1.0, False, 1, 8, 8, 3, 3, 3)] = WI.ImageEntry(object(), object(), object())
     F.mark_packs_stale()
-    assert F._PACK_STATE['stale'] is True and ('rgbmat', 1) not in F._PACK_CACHE and len(F._PACK_CACHE) == 1
+    assert images.stale is True and rgb not in images._entries and len(images._entries) == 1
     F.clear_pack_cache()
-    assert not F._PACK_CACHE and F._PACK_STATE['stale'] is False
+    assert not images._entries and images.stale is False
 
 
 def test_rs_ag_chunk_arithmetic_with_a_fake_collective(monkeypatch):
