@@ -699,6 +699,34 @@ int32_t sg_intensity_hist_max_bins(void);      /* the LDS image of a block: 8191
 int sg_intensity_hist(const void* x, sg_src_dtype dt, int64_t rows, int64_t row_elems, float scale, float shift, int32_t lo,
                       int32_t bins, int64_t* out, int accumulate, sg_stream_t st);
 
+/* ---- sample previews (csrc/render.hip; preview.py) ----------------------------------------------------------------
+ * One launch renders one VIEW of every sample of x [n, d, h, w, c] (the source type dt: any sg_src_dtype, SG_SRC_BF16 included;
+ * contiguous, on the device; channel `channel` of c) into the DEVICE u8 canvas [canvas_h, canvas_w].  With c == 1 NDHWC is the
+ * memory of NCDHW: a batch of the networks, a volume file and a row of a resident table pass as they are.
+ * axis: the collapsed axis, 0 = D, 1 = H, 2 = W; the image's rows and columns are the remaining two in their original order:
+ *   axis 0 -> H x W (axial), axis 1 -> D x W (coronal), axis 2 -> D x H (sagittal).
+ * Per image pixel, in f32 unless said otherwise, exactly and in this order:
+ *   v = x[index along the axis]                          SG_VIEW_SLICE
+ *       the maximum over the axis, from -inf              SG_VIEW_MAX   NaN voxels are ignored; an all-NaN column gives -inf
+ *       f32(sum over the axis / extent)                   SG_VIEW_MEAN  the sum in f64 (any order), one f64 division, one rounding
+ *   t = v * scale + shift                                two correctly rounded operations, never fused, as in sg_intensity_hist
+ *   u = (t - lo) * inv                                   inv: the caller's f32(255.0 / (f64(hi) - f64(lo)))
+ *   g = u8(floorf(fminf(fmaxf(u, 0), 255) + 0.5f))       a NaN u gives 0
+ * g is written zoom_r x zoom_c times (nearest repeat): sample i's tile of (rows * zoom_r) x (columns * zoom_c) pixels starts at
+ * (r0 + (i / grid_cols) * pitch_r, c0 + (i % grid_cols) * pitch_c).  Pixels outside the tiles are not touched: the caller zeroes
+ * the canvas.  No atomics: every pixel has one writer.  Every offset is 64-bit.  x need only be aligned to its element size
+ * (16-byte loads where c == 1, from the first 16-byte boundary; an element path in front of it and behind the last whole load).
+ * SG_EINVAL before any launch: a NULL pointer with work to do; n, d, h, w < 0 or c < 1; channel outside [0, c); an unknown dt,
+ * axis or mode; a slice index outside the axis; a zoom < 1 or grid_cols < 1; hi <= lo or a non-finite lo, hi or scale; a negative
+ * canvas size, origin or pitch; a pitch smaller than the tile where a second tile follows along it; ANY TILE THAT DOES NOT LIE
+ * WHOLLY INSIDE THE CANVAS (computed on the host from n, the tile size and the pitches: nothing out of bounds can be written).
+ * SG_EALIGN: x not aligned to its element size.  n == 0 or an empty extent: SG_OK, nothing launched. */
+enum { SG_VIEW_SLICE = 0, SG_VIEW_MAX = 1, SG_VIEW_MEAN = 2 };
+int sg_render_view(const void* x, sg_src_dtype dt, int64_t n, int64_t d, int64_t h, int64_t w, int32_t c, int32_t channel,
+                   int32_t axis, int32_t mode, int64_t index, int32_t zoom_r, int32_t zoom_c, float scale, float shift, float lo,
+                   float hi, float inv, uint8_t* canvas, int64_t canvas_h, int64_t canvas_w, int64_t r0, int64_t c0,
+                   int32_t grid_cols, int64_t pitch_r, int64_t pitch_c, sg_stream_t st);
+
 /* ---- opt-in kernel timing (used by bench.py's roofline leg) ------------------------------------- */
 /* When enabled, every sg_conv3d_fwd / sg_conv3d_wgrad launch is bracketed by hipEvents on its stream.
  * sg_prof_collect synchronises those events and returns, per kind (0 = conv fwd, 1 = wgrad) and per

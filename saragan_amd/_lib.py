@@ -21,6 +21,8 @@ SG_AUGF_ADJOINT, SG_AUGF_LINEAR = 1, 2
 SG_SRC_U8, SG_SRC_I8, SG_SRC_I16, SG_SRC_U16, SG_SRC_F16, SG_SRC_F32, SG_SRC_BF16 = 0, 1, 2, 3, 4, 5, 6
 # sg_intensity_hist_max_bins(), restated so that argument checks run before the library is loaded (a GPU test compares the two)
 INTENSITY_HIST_MAX_BINS = 8191
+# sg_render_view modes
+SG_VIEW_SLICE, SG_VIEW_MAX, SG_VIEW_MEAN = 0, 1, 2
 
 
 class ConvShape(C.Structure):
@@ -163,6 +165,8 @@ SIGNATURES = {
     'sg_gather_rows': (C.c_int, [_p, C.c_int, _i64, _i64, _p, _i32, _p, _i32, _f, _f, _p]),
     'sg_intensity_hist_max_bins': (_i32, []),
     'sg_intensity_hist': (C.c_int, [_p, C.c_int, _i64, _i64, _f, _f, _i32, _i32, _p, C.c_int, _p]),
+    'sg_render_view': (C.c_int, [_p, C.c_int, _i64, _i64, _i64, _i64, _i32, _i32, _i32, _i32, _i64, _i32, _i32, _f, _f, _f, _f, _f,
+                                 _p, _i64, _i64, _i64, _i64, _i32, _i64, _i64, _p]),
     'sg_prof_enable': (C.c_int, [C.c_int]),
     'sg_prof_enabled': (C.c_int, []),
     'sg_prof_collect': (C.c_int, [C.POINTER(ProfEntry), _i32, C.POINTER(_i32)]),

@@ -48,7 +48,26 @@ def build_parser():
                    help='(new flag) "v1,...,vL": the label row every sample is generated with; for checkpoints of conditional runs')
     p.add_argument('--conditioning_path', type=str, default=None,
                    help='(new flag) a float [num_samples, L] .npy: one label row per sample, in output order')
+    p.add_argument('--png', default=False, action='store_true',
+                   help='(new flag) also write fake_images_{phase}.png, a contact sheet of the samples (saragan_amd.preview)')
+    p.add_argument('--preview_views', type=str, default='slice_d,slice_h,max_h', help='(new flag) with --png: the row bands')
+    p.add_argument('--preview_window', type=str, default=None,
+                   help='(new flag) with --png: LO,HI in data units; default data_mean - data_stddev,data_mean + 2 data_stddev')
+    p.add_argument('--preview_zoom_d', type=int, default=1, help='(new flag) with --png: repeat the D rows of coronal / sagittal views')
     return p
+
+
+def write_sheet(args, fake_batch, path, device):
+    """--png: the sheet of the saved samples, re-normalised (what the generator gave) and mapped back by scale = stddev, shift =
+    mean, as the training loop's previews are."""
+    from . import preview
+    window = (preview.default_window(args.data_mean, args.data_stddev) if args.preview_window is None
+              else preview.parse_window(args.preview_window))
+    x = np.ascontiguousarray(data.normalize_numpy(fake_batch, args.data_mean, args.data_stddev), dtype=np.float32)
+    scale, shift = (1.0, 0.0) if args.data_mean is None else (float(args.data_stddev), float(args.data_mean))
+    img = preview.sheet(torch.from_numpy(x).to(device), args.preview_views, window, scale, shift, args.preview_zoom_d)
+    return preview.write_png(path, img, dict(phase=args.phase, views=args.preview_views, window=f'{window[0]},{window[1]}',
+                                             seed=args.seed, model=args.model_path))
 
 
 def label_rows(args):
@@ -130,6 +149,8 @@ def main(args, device='cuda'):
     print(f'Maximum of generated image 1 after inverting normalization: {np.max(fake_batch[0, ...])}')
     out = os.path.join(logdir, f'fake_images_{phase}.npy')
     np.save(out, fake_batch)
+    if getattr(args, 'png', False):
+        write_sheet(args, fake_batch, os.path.join(logdir, f'fake_images_{phase}.png'), device)
     return out
 
 

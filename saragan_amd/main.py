@@ -180,6 +180,20 @@ def build_parser():
                         '--hist_range=LO,HI')
     p.add_argument('--hist_levels', type=int, default=1,
                    help='with --compute_intensity_hist: 1 = the volumes; N = plus N - 1 detail levels of the Laplacian pyramid')
+    # (not in the reference) sample previews: PNG contact sheets of fixed latents under <logdir>/previews (preview.py)
+    p.add_argument('--preview_every_nsteps', type=int, default=0,
+                   help='(not in the reference) write a sheet of the fixed latents every N images (0: off)')
+    p.add_argument('--preview_samples', type=int, default=8, help='(not in the reference) fixed latents per sheet')
+    p.add_argument('--preview_views', type=str, default='slice_d,slice_h,max_h',
+                   help='(not in the reference) row bands of a sheet: slice_d|h|w[:INDEX], max_d|h|w, mean_d|h|w')
+    p.add_argument('--preview_window', type=none_or_str, default=None,
+                   help='(not in the reference) LO,HI in data units, drawn black to white; default: the reference\'s clip range '
+                        '[-1, 2] of normalised values, data_mean - data_stddev,data_mean + 2 data_stddev.  A negative LO is '
+                        'written --preview_window=LO,HI')
+    p.add_argument('--preview_zoom_d', type=int, default=1,
+                   help='(not in the reference) repeat the D rows of coronal and sagittal views (D is size / 4 in this data)')
+    p.add_argument('--preview_interp', type=int, default=0,
+                   help='(not in the reference) K > 1: a second sheet of K latents on the great arc between fixed latents 0 and 1')
     p.add_argument('--dtype', default='bf16', choices=['bf16', 'f32'], help='activation / MFMA input type (new flag)')
     p.add_argument('--max_steps_per_phase', type=int, default=None, help='smoke runs: cap the steps per phase (new flag)')
     return p
@@ -279,6 +293,37 @@ def finalize_hist_args(args):
     return args
 
 
+def finalize_preview_args(args):
+    """--preview_*: the views and the window are parsed (args.preview_views: [(mode, axis, index)], args.preview_window: (lo,
+    hi) in data units); refused at start-up where the run could not use them."""
+    every = getattr(args, 'preview_every_nsteps', 0) or 0
+    interp = getattr(args, 'preview_interp', 0) or 0
+    if every < 0:
+        raise SystemExit('--preview_every_nsteps must be >= 0 (0 turns the previews off)')
+    if interp and not every:
+        raise SystemExit('--preview_interp needs --preview_every_nsteps')
+    if interp < 0 or interp == 1:
+        raise SystemExit('--preview_interp is 0 (off) or the number K > 1 of interpolated latents')
+    if not every:
+        return args
+    from . import preview
+    if args.preview_samples < 1 or (interp and args.preview_samples < 2):
+        raise SystemExit('--preview_samples must be >= 1 (>= 2 with --preview_interp: the arc runs from latent 0 to latent 1)')
+    if args.preview_zoom_d < 1:
+        raise SystemExit('--preview_zoom_d must be >= 1')
+    try:
+        args.preview_views = preview.parse_views(args.preview_views)
+    except ValueError as e:
+        raise SystemExit(f'--preview_views: {e}')
+    if not isinstance(args.preview_window, tuple):
+        try:
+            args.preview_window = (preview.default_window(args.data_mean, args.data_stddev) if args.preview_window is None
+                                   else preview.parse_window(args.preview_window))
+        except ValueError as e:
+            raise SystemExit(f'--preview_window: {e}')
+    return args
+
+
 def finalize_args(args):
     """main.py:384-411 post-parse defaults: the discriminator inherits the generator's optimiser settings unless
     the --d_use_different_* switches are given; presets fill missing kernel/filter specs."""
@@ -290,6 +335,7 @@ def finalize_args(args):
     finalize_augment_args(args)
     finalize_mbstd_args(args)
     finalize_hist_args(args)
+    finalize_preview_args(args)
     if getattr(args, 'conditioning_path', None) and args.architecture != 'pgan':
         raise SystemExit(f'--conditioning_path is offered for the pgan architecture only, got {args.architecture!r}')
     if getattr(args, 'sn_iterations', 1) != 1 and not getattr(args, 'd_spectral_norm', False):

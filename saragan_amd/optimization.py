@@ -510,6 +510,20 @@ class StepGraph:
         """conditioning=... for the loss builders of a conditional graph (none otherwise: their calls are what they were)."""
         return {} if self._cond is None else dict(conditioning=self._cond)
 
+    def generate(self, z, cond=None):
+        """The generator's forward alone, under the current weights and alpha, for the CALLER's latents z [n, latent_dim] (any
+        n; cond: the [n, L] label rows of a conditional graph): no discriminator pass, no gradient, and no draw from any random
+        stream -- what a gen_sample fetch runs on its own draw, and what the previews (preview.py) run on their fixed latents."""
+        c = self.cfg
+        self._ensure_flat()
+        cond = self._labels(cond, z.shape[0])
+        kw = {} if cond is None else dict(conditioning=cond.to(z.device))
+        with use_store(self.store), torch.no_grad():
+            alpha = float(c['alpha'].eval()) if isinstance(c['alpha'], ScalarVariable) else float(c['alpha'])
+            sample = c['generator'](z, alpha, c['phase'], c['base_shape'], activation=c['activation'],
+                                    kernel_spec=c['kernel_spec'], filter_spec=c['filter_spec'], param=c['leakiness'], **kw)
+        return sample.detach()
+
     def run(self, fetches, feed, cond=None):
         c = self.cfg
         self._ensure_flat()
@@ -524,13 +538,8 @@ class StepGraph:
             n = c['placeholder'].shape[0]
             dev = self.store.device if real is None else real.device
             cond = self._labels(cond, n)
-            kw = {} if cond is None else dict(conditioning=cond.to(dev))
-            with use_store(self.store), torch.no_grad():
-                alpha = float(c['alpha'].eval()) if isinstance(c['alpha'], ScalarVariable) else float(c['alpha'])
-                z = L._rng(dev).latent(n, c['latent_dim'], dev)
-                sample = c['generator'](z, alpha, c['phase'], c['base_shape'], activation=c['activation'],
-                                        kernel_spec=c['kernel_spec'], filter_spec=c['filter_spec'], param=c['leakiness'], **kw)
-            return [sample.detach() for _ in fetches]
+            sample = self.generate(L._rng(dev).latent(n, c['latent_dim'], dev), cond)
+            return [sample for _ in fetches]
         self._cond = self._labels(cond, real.shape[0])
         self._stepped = True
         self._refuse_spectral_with_adasum()

@@ -1,5 +1,6 @@
-"""Reads of typed device tables: batches gathered from a resident dataset (dataset.ResidentLoader) and
-voxel-intensity histograms (metrics/intensity_metrics.py).  Re-exported by functional."""
+"""Reads of typed device tables: batches gathered from a resident dataset (dataset.ResidentLoader),
+voxel-intensity histograms (metrics/intensity_metrics.py) and rendered views (preview.py).
+Re-exported by functional."""
 import math
 
 import torch
@@ -117,3 +118,108 @@ def intensity_hist(x, lo, hi, scale=1.0, shift=0.0, pooled=False, out=None, accu
         check(lib.sg_intensity_hist(_ptr(x), HIST_DT[x.dtype], rows, row_elems, float(scale), float(shift), lo, bins, _ptr(out),
                                     1 if accumulate else 0, _stream()), 'sg_intensity_hist')
     return out
+
+
+# ---- sample previews: one view of every sample of a batch, rendered into a u8 canvas
+VIEW_MODES = {'slice': _lib.SG_VIEW_SLICE, 'max': _lib.SG_VIEW_MAX, 'mean': _lib.SG_VIEW_MEAN}
+VIEW_AXES = {'d': 0, 'h': 1, 'w': 2}
+
+
+def view_volumes(x):
+    """(x, (n, d, h, w, c)): the NDHWC reading of a batch for render_view -- [n, d, h, w]; [n, 1, d, h, w] in either memory format
+    (with one channel NCDHW and NDHWC are the same memory); or [n, d, h, w, c]."""
+    if not torch.is_tensor(x):
+        raise TypeError(f'render_view: expected a tensor, got {type(x).__name__}')
+    if x.dtype not in HIST_DT:
+        raise TypeError(f'render_view: inputs are uint8, int8, int16, uint16, float16, bfloat16 or float32, got {x.dtype}')
+    if x.dim() == 4:
+        n, d, h, w = x.shape
+        c = 1
+    elif x.dim() == 5 and x.shape[1] == 1:      # (a second axis of size 1 always reads as the channel axis of NCDHW)
+        n, _, d, h, w = x.shape
+        c = 1
+        if not x.is_contiguous() and x.is_contiguous(memory_format=torch.channels_last_3d):
+            x = x.permute(0, 2, 3, 4, 1)      # the same memory, contiguous as [n, d, h, w, 1]
+    elif x.dim() == 5:
+        n, d, h, w, c = x.shape
+    else:
+        raise ValueError(f'render_view: expected [n, d, h, w], [n, 1, d, h, w] or [n, d, h, w, c], got {tuple(x.shape)}')
+    if not x.is_contiguous():
+        raise ValueError('render_view: expected a contiguous tensor')
+    return x, (n, d, h, w, c)
+
+
+def view_tile(dims, axis, zoom=(1, 1)):
+    """(rows, columns) of one sample's tile: the two axes that remain, in their original order, times the zoom."""
+    d, h, w = dims
+    rows, cols = ((h, w), (d, w), (d, h))[axis]
+    return rows * zoom[0], cols * zoom[1]
+
+
+def render_view(x, axis, mode, index=None, window=(-1.0, 2.0), scale=1.0, shift=0.0, zoom=(1, 1), channel=0, canvas=None,
+                origin=(0, 0), grid_cols=None, pitch=None):
+    """u8 [canvas_h, canvas_w]: one view of every sample of x ([n, d, h, w], [n, 1, d, h, w] or [n, d, h, w, c]; u8 / i8 / i16 /
+    u16 / f16 / bf16 / f32, contiguous, on the device), one launch (sg_render_view).  axis: the collapsed axis, 0 = D, 1 = H,
+    2 = W (or 'd' / 'h' / 'w'); mode 'slice' (plane `index`, default the middle one, extent // 2), 'max' or 'mean'.  The
+    grey level of v is floor(clamp(((v * scale + shift) - lo) * inv, 0, 255) + 0.5) in f32, inv = f32(255 / (hi - lo)), window =
+    (lo, hi) in data units.  zoom = (rows, columns): integer nearest repeat.  Sample i's tile starts at origin + (i // grid_cols *
+    pitch[0], i % grid_cols * pitch[1]); grid_cols defaults to n (one row of tiles) and pitch to the tile's size.  canvas: a u8
+    tensor to draw into (pixels outside the tiles keep their values); None: a zeroed one that just holds the tiles."""
+    x, (n, d, h, w, c) = view_volumes(x)
+    axis = VIEW_AXES.get(axis, axis)
+    if axis not in (0, 1, 2):
+        raise ValueError(f'render_view: axis is 0 (D), 1 (H) or 2 (W), got {axis!r}')
+    if mode not in VIEW_MODES:
+        raise ValueError(f'render_view: mode is slice, max or mean, got {mode!r}')
+    extent = (d, h, w)[axis]
+    if mode == 'slice':
+        index = extent // 2 if index is None else int(index)
+        if extent and not 0 <= index < extent:
+            raise ValueError(f'render_view: slice {index} lies outside the axis of {extent} planes')
+    elif index is not None:
+        raise ValueError(f'render_view: index belongs to slices, not to {mode}')
+    lo, hi = float(window[0]), float(window[1])
+    if not (math.isfinite(lo) and math.isfinite(hi)) or hi <= lo:
+        raise ValueError(f'render_view: the window [{lo}, {hi}] is empty or not finite')
+    if not math.isfinite(float(scale)):
+        raise ValueError(f'render_view: scale {scale} is not finite')
+    zoom = (int(zoom[0]), int(zoom[1]))
+    if zoom[0] < 1 or zoom[1] < 1:
+        raise ValueError(f'render_view: zooms are integers >= 1, got {zoom}')
+    if not 0 <= int(channel) < c:
+        raise ValueError(f'render_view: channel {channel} of {c}')
+    tile = view_tile((d, h, w), axis, zoom)
+    grid_cols = max(n, 1) if grid_cols is None else int(grid_cols)
+    if grid_cols < 1:
+        raise ValueError(f'render_view: grid_cols {grid_cols} < 1')
+    pitch = tile if pitch is None else (int(pitch[0]), int(pitch[1]))
+    origin = (int(origin[0]), int(origin[1]))
+    down, across = (n - 1) // grid_cols + 1 if n else 0, min(n, grid_cols)
+    if min(origin) < 0 or (down > 1 and pitch[0] < tile[0]) or (across > 1 and pitch[1] < tile[1]):
+        raise ValueError(f'render_view: origin {origin} is negative or pitch {pitch} is smaller than the tile {tile}')
+    need = (origin[0] + (down - 1) * pitch[0] + tile[0], origin[1] + (across - 1) * pitch[1] + tile[1]) if n else (0, 0)
+    if canvas is None:
+        shape = need
+    elif (not torch.is_tensor(canvas) or canvas.dim() != 2 or canvas.dtype != torch.uint8 or canvas.device != x.device
+          or not canvas.is_contiguous()):
+        raise ValueError(f'render_view: canvas must be a contiguous 2-D uint8 tensor on {x.device}')
+    else:
+        shape = tuple(canvas.shape)
+        if need[0] > shape[0] or need[1] > shape[1]:
+            raise ValueError(f'render_view: the tiles end at {need}, outside the canvas {shape}')
+    if not x.is_cuda:
+        raise ValueError('render_view: the input is a device tensor (there is no CPU path)')
+    lib = _lib.load()
+    if canvas is None:
+        canvas = torch.zeros(shape, device=x.device, dtype=torch.uint8)
+    import numpy as np
+    lo32, hi32 = np.float32(lo), np.float32(hi)      # the window as the kernel holds it
+    if not hi32 > lo32:
+        raise ValueError(f'render_view: the window [{lo}, {hi}] is empty in float32')
+    inv = float(np.float32(255.0 / (float(hi32) - float(lo32))))
+    with torch.cuda.device(x.device):
+        check(lib.sg_render_view(_ptr(x), HIST_DT[x.dtype], n, d, h, w, c, int(channel), axis, VIEW_MODES[mode],
+                                 index if mode == 'slice' else 0, zoom[0], zoom[1], float(scale), float(shift), float(lo32),
+                                 float(hi32), inv, _ptr(canvas), shape[0], shape[1], origin[0], origin[1], grid_cols, pitch[0],
+                                 pitch[1], _stream()), 'sg_render_view')
+    return canvas

@@ -121,6 +121,11 @@ def _run_training(args, device, max_steps_per_phase, log_every):
             raise NotImplementedError(f'conditioning (--conditioning_path) is offered for the pgan architecture only, got '
                                       f'{args.architecture!r}')
         label_table = load_label_table(args.conditioning_path, args.dataset_path, args.start_shape, num_phases)
+    previews = None      # (not in the reference) --preview_every_nsteps: PNG sheets of fixed latents, rank 0
+    preview_every = getattr(args, 'preview_every_nsteps', 0) or 0
+    if preview_every and verbose:
+        from .preview import LoopPreviews
+        previews = LoopPreviews(args, logdir, device, label_table, tap=getattr(args, '_preview_tap', None))
 
     for phase in range(1, ending_phase + 1):
         np.random.seed(seed); random.seed(seed); torch.manual_seed(seed)   # :102-109
@@ -240,6 +245,8 @@ def _run_training(args, device, max_steps_per_phase, log_every):
         loader = make_loader(npy_data, batch_size, horovod, args.data_mean, args.data_stddev, device,
                              getattr(args, 'device_dataset_gib', 0.0))
         local_step = 0
+        if previews is not None:
+            previews.reals(npy_data.scratch_files, phase)
         mixing_bool = args.mixing_nimg > 0
         t_phase, imgs, d_loss, g_loss = time.time(), 0, float('nan'), float('nan')
         while True:
@@ -256,6 +263,7 @@ def _run_training(args, device, max_steps_per_phase, log_every):
                     save_checkpoint(store, os.path.join(logdir, f'model_{phase}_ckpt_{global_step}'))
             batch = loader.next()
             metrics_summary_bool = local_step % getattr(args, 'metrics_every_nsteps', 128) < batch_size      # :443
+            preview_bool = previews is not None and local_step % preview_every < batch_size      # (the same rule)
             if mixing_bool:      # quirk Q4: previous-phase variables stay frozen while alpha > 0
                 train_g, train_d = train_gen_freeze or train_gen, train_disc_freeze or train_disc
             else:
@@ -290,6 +298,8 @@ def _run_training(args, device, max_steps_per_phase, log_every):
                 sess.run(ema.assign_ema_weights())
                 run_metrics(npy_data_validation, num_metric_samples, suffix='_EMA')
                 sess.run(ema.restore_original_weights())
+            if preview_bool:
+                previews.fakes(sess, graph, ema, phase, global_step, batch_size, f'{global_step:09d}')
             if want_log:
                 print_summary_to_stdout(global_step, int(in_phase_step), img_s, local_img_s, d_loss, g_loss,
                                         float(d_lr_val), float(g_lr_val), alpha)
@@ -321,6 +331,8 @@ def _run_training(args, device, max_steps_per_phase, log_every):
                             batch_size=batch_size, steps=local_step // batch_size)
         if aug is not None:
             stats[phase]['augment_p'] = float(aug.p)
+        if previews is not None:      # the phase's last look, before the EMA weights become the weights
+            previews.fakes(sess, graph, ema, phase, global_step, batch_size, 'final', grid=True)
         # quirk Q5: the end-of-phase checkpoint holds the EMA weights of G AND D; the next phase starts from them
         sess.run(ema.ema_update_weights())
         if horovod:
