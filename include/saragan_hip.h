@@ -727,6 +727,51 @@ int sg_render_view(const void* x, sg_src_dtype dt, int64_t n, int64_t d, int64_t
                    float hi, float inv, uint8_t* canvas, int64_t canvas_h, int64_t canvas_w, int64_t r0, int64_t c0,
                    int32_t grid_cols, int64_t pitch_r, int64_t pitch_c, sg_stream_t st);
 
+/* ---- the per-phase dataset pyramid (csrc/pyramid.hip; prepare_data.py) ---------------------------------------------
+ * One launch reads a batch of source volumes x [n, sd, sh, sw] (the source type dt: any sg_src_dtype except SG_SRC_BF16;
+ * contiguous, on the device, aligned to its element size) ONCE and writes `levels` (1 .. SG_PYRAMID_LEVELS_PER_LAUNCH) levels of
+ * its block-reduction pyramid: out[i], i < levels, is [n, D >> i, H >> i, W >> i] of the output type out_dt (SG_SRC_U16,
+ * SG_SRC_I16 or SG_SRC_F32; integer sources take any of the three, f16 / f32 sources SG_SRC_F32 only).  `out` is a HOST array
+ * of `levels` device pointers.
+ * The window: target voxel (td, th, tw) of the target shape (D, H, W) is source voxel (td + off_d, th + off_h, tw + off_w); the
+ * offsets may be negative or run past the source, and a target voxel whose source index lies outside [0, extent) on any axis
+ * reads pad_value.  Nothing outside the source is read.
+ * Integer sources (u8, i8, i16, u16) use the *_i scalars, and exactly, per output voxel o of level i (its cube: the 2^i x 2^i
+ * x 2^i target voxels from 2^i * o):
+ *   v = int32(x or pad_value) - intercept                 (|intercept|, |pad_value| <= 2^30: v is a 32-bit integer)
+ *   s = the sum of v over the cube, a 64-bit integer      SG_PYR_MEAN
+ *       the maximum of v over the cube                    SG_PYR_MAX
+ *   q = s / 8^i truncated toward zero                     SG_PYR_MEAN (integers; -1.5 gives -1);   q = s for SG_PYR_MAX
+ *   stored: clamp(q, clip_lo, clip_hi) as out_dt          u16 / i16
+ *           clamp(f32(f64(s) / 8^i), f32(clip_lo), f32(clip_hi))     SG_SRC_F32 (one rounding; MAX: f32(s))
+ * which for MEAN is bit for bit np.clip(block_reduce(v, 2^i, np.average), lo, hi).astype(T): an f64 sum of integers under 2^53 is
+ * exact in any order, the division by a power of two is exact, and clipping then truncating equals truncating then clamping
+ * for integer bounds.
+ * Float sources (f16, f32) use the *_f scalars:
+ *   v = f32(x or pad_value) - intercept                   one f32 rounding
+ *   s = the f64 sum of v over the cube, in any order      SG_PYR_MEAN: a NaN voxel makes its cubes NaN
+ *       the maximum over the cube from -inf               SG_PYR_MAX: NaN voxels are ignored, an all-NaN cube gives -inf
+ *   stored: clamp(f32(s / 8^i), clip_lo, clip_hi)         one f64 division, one rounding, as SG_VIEW_MEAN; a NaN stays NaN
+ * Level i is built from level i - 1's unclamped, untruncated partials s (int64, f64, or the running maxima), never from stored
+ * values.  No output voxel has two writers; no atomics touch the outputs.  Every offset is 64-bit.  Source rows are read with
+ * 16-byte loads from each row's first 16-byte boundary, the elements in front of it and behind the last whole load one by one.
+ * A pyramid is at most SG_PYRAMID_LEVELS_PER_LAUNCH levels deep (a 128 x 512 x 512 volume down to 4 x 16 x 16): there is no entry
+ * that continues from the partials of a launch's deepest level.
+ * stats (may be NULL; integer out_dt only, ignored for SG_SRC_F32): DEVICE int64 [n][levels][4] = the sum, the sum of squares,
+ * the minimum and the maximum of the STORED values of every level of every sample.  Set to (0, 0, INT64_MAX, INT64_MIN) on the
+ * stream first, then accumulated with integer atomics, one per block after a block-level reduction: exact, independent of order.
+ * SG_EINVAL before any launch: a NULL pointer with work to do; a negative extent; levels outside [1, 6]; a target extent not
+ * divisible by 2^(levels-1); an unknown dt, mode or out_dt, SG_SRC_BF16; a float
+ * source with an integer out_dt; clip_lo > clip_hi (a NaN bound), integer bounds outside an integer out_dt; |intercept_i| or
+ * |pad_i| > 2^30; an extent or |offset| > 2^29.  SG_EALIGN: x, an output or stats not aligned to its element size.  n == 0 or an empty
+ * target: SG_OK, nothing launched. */
+#define SG_PYRAMID_LEVELS_PER_LAUNCH 6
+enum { SG_PYR_MEAN = 0, SG_PYR_MAX = 1 };
+int sg_block_pyramid(const void* x, sg_src_dtype dt, int64_t n, int64_t sd, int64_t sh, int64_t sw, int64_t D, int64_t H, int64_t W,
+                     int64_t off_d, int64_t off_h, int64_t off_w, int32_t levels, int32_t mode, int32_t intercept_i, int32_t pad_i,
+                     int32_t clip_lo_i, int32_t clip_hi_i, float intercept_f, float pad_f, float clip_lo_f, float clip_hi_f,
+                     sg_src_dtype out_dt, void* const* out, int64_t* stats, sg_stream_t st);
+
 /* ---- opt-in kernel timing (used by bench.py's roofline leg) ------------------------------------- */
 /* When enabled, every sg_conv3d_fwd / sg_conv3d_wgrad launch is bracketed by hipEvents on its stream.
  * sg_prof_collect synchronises those events and returns, per kind (0 = conv fwd, 1 = wgrad) and per

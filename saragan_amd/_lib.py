@@ -23,6 +23,9 @@ SG_SRC_U8, SG_SRC_I8, SG_SRC_I16, SG_SRC_U16, SG_SRC_F16, SG_SRC_F32, SG_SRC_BF1
 INTENSITY_HIST_MAX_BINS = 8191
 # sg_render_view modes
 SG_VIEW_SLICE, SG_VIEW_MAX, SG_VIEW_MEAN = 0, 1, 2
+# sg_block_pyramid modes and the levels one launch writes
+SG_PYR_MEAN, SG_PYR_MAX = 0, 1
+SG_PYRAMID_LEVELS_PER_LAUNCH = 6
 
 
 class ConvShape(C.Structure):
@@ -167,6 +170,8 @@ SIGNATURES = {
     'sg_intensity_hist': (C.c_int, [_p, C.c_int, _i64, _i64, _f, _f, _i32, _i32, _p, C.c_int, _p]),
     'sg_render_view': (C.c_int, [_p, C.c_int, _i64, _i64, _i64, _i64, _i32, _i32, _i32, _i32, _i64, _i32, _i32, _f, _f, _f, _f, _f,
                                  _p, _i64, _i64, _i64, _i64, _i32, _i64, _i64, _p]),
+    'sg_block_pyramid': (C.c_int, [_p, C.c_int, _i64, _i64, _i64, _i64, _i64, _i64, _i64, _i64, _i64, _i64, _i32, _i32, _i32, _i32,
+                                   _i32, _i32, _f, _f, _f, _f, C.c_int, C.POINTER(_p), _p, _p]),
     'sg_prof_enable': (C.c_int, [C.c_int]),
     'sg_prof_enabled': (C.c_int, []),
     'sg_prof_collect': (C.c_int, [C.POINTER(ProfEntry), _i32, C.POINTER(_i32)]),

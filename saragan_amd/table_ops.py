@@ -1,6 +1,6 @@
 """Reads of typed device tables: batches gathered from a resident dataset (dataset.ResidentLoader),
-voxel-intensity histograms (metrics/intensity_metrics.py) and rendered views (preview.py).
-Re-exported by functional."""
+voxel-intensity histograms (metrics/intensity_metrics.py), rendered views (preview.py) and the
+dataset pyramid of full-size volumes (prepare_data.py).  Re-exported by functional."""
 import math
 
 import torch
@@ -223,3 +223,155 @@ def render_view(x, axis, mode, index=None, window=(-1.0, 2.0), scale=1.0, shift=
                                  float(hi32), inv, _ptr(canvas), shape[0], shape[1], origin[0], origin[1], grid_cols, pitch[0],
                                  pitch[1], _stream()), 'sg_render_view')
     return canvas
+
+
+# ---- the per-phase dataset pyramid: pad / crop to the target, subtract the intercept, block-reduce by 2, 4, ..., clip, cast
+PYR_MODES = {'mean': _lib.SG_PYR_MEAN, 'max': _lib.SG_PYR_MAX}
+PYR_ANCHORS = ('center', 'start', 'end')
+PYR_OUT_DT = {torch.uint16: _lib.SG_SRC_U16, torch.int16: _lib.SG_SRC_I16, torch.float32: _lib.SG_SRC_F32}
+_PYR_RANGE = {torch.uint16: (0, 65535), torch.int16: (-32768, 32767), torch.float32: (-2 ** 31, 2 ** 31 - 1)}
+_PYR_SCALAR_MAX = 2 ** 30      # |intercept|, |pad_value| of integer sources: x - intercept stays a 32-bit integer
+_PYR_EXTENT_MAX = 2 ** 29
+
+
+def pyramid_offsets(source, target, anchor=('center',) * 3):
+    """Per axis the source index of target index 0.  'center' is the original's pad_to / crop_to: a short axis gets
+    floor((T - S) / 2) voxels in front, a long one starts at S // 2 - T // 2; 'start': offset 0 (pad and crop at the end); 'end':
+    pad in front and crop from the front."""
+    if isinstance(anchor, str):
+        anchor = (anchor,) * 3
+    if len(anchor) != 3 or any(a not in PYR_ANCHORS for a in anchor):
+        raise ValueError(f'block_pyramid: anchor is center, start or end per axis, got {anchor!r}')
+    off = []
+    for s, t, a in zip(source, target, anchor):
+        if a == 'start':
+            off.append(0)
+        elif a == 'end':
+            off.append(s - t)
+        else:
+            off.append(-((t - s) // 2) if s < t else s // 2 - t // 2)
+    return tuple(off)
+
+
+def _pyramid_numpy(x, target, off, levels, mode, intercept, pad, lo, hi, out_dtype, want_stats):
+    """The CPU path: the kernel's definition in numpy (windowed copy by index, integer sums, integer division toward zero)."""
+    import numpy as np
+    a = x.numpy()
+    n, is_int = a.shape[0], a.dtype.kind in 'iu'
+    out_np = {torch.uint16: np.uint16, torch.int16: np.int16, torch.float32: np.float32}[out_dtype]
+    if is_int:
+        v = np.full((n,) + tuple(target), pad - intercept, np.int64 if mode == 'mean' else np.int32)
+    else:
+        v = np.full((n,) + tuple(target), np.float32(pad) - np.float32(intercept), np.float32)
+    t0 = [max(0, -o) for o in off]
+    t1 = [min(t, s - o) for t, s, o in zip(target, a.shape[1:], off)]
+    if all(p < q for p, q in zip(t0, t1)):
+        dst = (slice(None),) + tuple(slice(p, q) for p, q in zip(t0, t1))
+        src = (slice(None),) + tuple(slice(p + o, q + o) for p, q, o in zip(t0, t1, off))
+        v[dst] = a[src].astype(np.int64) - intercept if is_int else a[src].astype(np.float32) - np.float32(intercept)
+    if mode == 'mean':
+        part = v if is_int else v.astype(np.float64)
+    else:
+        part = v if is_int else np.fmax(v, np.float32(-np.inf))      # (the maximum from -inf: a NaN voxel is ignored)
+    outs, stats = [], np.zeros((n, levels, 4), np.int64)
+    for i in range(levels):
+        if i:
+            d, h, w = part.shape[1:]
+            cubes = part.reshape(n, d // 2, 2, h // 2, 2, w // 2, 2)
+            with np.errstate(invalid='ignore'):
+                part = cubes.sum(axis=(2, 4, 6)) if mode == 'mean' else cubes.max(axis=(2, 4, 6))
+        if out_np is np.float32:
+            with np.errstate(invalid='ignore'):
+                r = (part.astype(np.float64) / np.float64(8 ** i)).astype(np.float32) if mode == 'mean' else part.astype(np.float32)
+                stored = np.clip(r, np.float32(lo), np.float32(hi))
+        else:
+            q = part.astype(np.int64)
+            if mode == 'mean' and i:
+                q = np.where(q < 0, -((-q) >> (3 * i)), q >> (3 * i))      # toward zero
+            stored = np.clip(q, lo, hi).astype(out_np)
+            s = stored.reshape(n, -1).astype(np.int64)
+            stats[:, i] = np.stack([s.sum(1), (s * s).sum(1), s.min(1), s.max(1)], axis=1)
+        outs.append(torch.from_numpy(np.ascontiguousarray(stored)))
+    return outs, (torch.from_numpy(stats) if want_stats else None)
+
+
+def block_pyramid_launch(x, target, off, levels, mode, intercept, pad, lo, hi, out_dtype, want_stats=False):
+    """One sg_block_pyramid launch on checked arguments, the window given by its offsets: (outs, stats)."""
+    import ctypes as C
+    lib = _lib.load()
+    n = x.shape[0]
+    is_int = not x.dtype.is_floating_point
+    outs = [torch.empty((n,) + tuple(t >> i for t in target), device=x.device, dtype=out_dtype) for i in range(levels)]
+    stats = torch.empty((n, levels, 4), device=x.device, dtype=torch.int64) if want_stats else None
+    ptrs = (C.c_void_p * levels)(*[o.data_ptr() for o in outs])
+    ii, ip, ilo, ihi = (int(intercept), int(pad), int(lo), int(hi)) if is_int else (0, 0, 0, 0)
+    fi, fp, flo, fhi = (0.0, 0.0, 0.0, 0.0) if is_int else (float(intercept), float(pad), float(lo), float(hi))
+    with torch.cuda.device(x.device):
+        check(lib.sg_block_pyramid(_ptr(x), SRC_DT[x.dtype], n, x.shape[1], x.shape[2], x.shape[3], target[0], target[1], target[2],
+                                   off[0], off[1], off[2], levels, PYR_MODES[mode], ii, ip, ilo, ihi, fi, fp, flo, fhi,
+                                   PYR_OUT_DT[out_dtype], ptrs, _ptr(stats), _stream()), 'sg_block_pyramid')
+    return outs, stats
+
+
+def block_pyramid(x, target, levels, reduce='mean', intercept=0, pad_value=None, clip=None, out_dtype=torch.uint16,
+                  anchor=('center',) * 3, stats=False):
+    """The dataset pyramid of a batch x [n, sd, sh, sw] (u8 / i8 / i16 / u16 / f16 / f32, contiguous): a list of `levels` tensors
+    [n, D >> i, H >> i, W >> i] of out_dtype (uint16, int16 or float32; float sources: float32), target = (D, H, W), every extent a
+    multiple of 2 ** (levels - 1).  Every volume is padded with pad_value (None: the intercept, so the padding is 0 after the
+    shift) or cropped to the target, anchored per axis (pyramid_offsets); then v = x - intercept, level i is the mean (integers:
+    the exact sum divided by 8 ** i toward zero -- the bits of np.clip(block_reduce(v, 2 ** i, np.average), lo, hi).astype(T)) or
+    the maximum over the 2 ** i cubes, clipped to clip = (lo, hi) (None: the output type's range).  On the device one
+    sg_block_pyramid launch reads x once and writes all levels, at most six.  stats=True: also the int64 [n, levels, 4] sum, sum of squares, minimum and maximum of the stored
+    values (integer out_dtype).  A CPU tensor takes a numpy path with the same integer definition."""
+    if not torch.is_tensor(x):
+        raise TypeError(f'block_pyramid: expected a tensor, got {type(x).__name__}')
+    if x.dtype not in SRC_DT:
+        raise TypeError(f'block_pyramid: sources are uint8, int8, int16, uint16, float16 or float32, got {x.dtype}')
+    if out_dtype not in PYR_OUT_DT:
+        raise TypeError(f'block_pyramid: out_dtype is uint16, int16 or float32, got {out_dtype}')
+    is_int = not x.dtype.is_floating_point
+    if not is_int and out_dtype != torch.float32:
+        raise TypeError(f'block_pyramid: a {x.dtype} source takes out_dtype float32, got {out_dtype}')
+    if x.dim() != 4 or not x.is_contiguous():
+        raise ValueError(f'block_pyramid: expected a contiguous [n, d, h, w] tensor, got {tuple(x.shape)}')
+    if reduce not in PYR_MODES:
+        raise ValueError(f'block_pyramid: reduce is mean or max, got {reduce!r}')
+    target = tuple(int(t) for t in target)
+    levels = int(levels)
+    if len(target) != 3 or min(target) < 0 or max(target + tuple(x.shape[1:])) > _PYR_EXTENT_MAX:
+        raise ValueError(f'block_pyramid: target is (D, H, W) with extents in [0, 2^29], got {target} for a source {tuple(x.shape[1:])}')
+    if not 1 <= levels <= _lib.SG_PYRAMID_LEVELS_PER_LAUNCH:
+        raise ValueError(f'block_pyramid: levels is 1 .. {_lib.SG_PYRAMID_LEVELS_PER_LAUNCH}, got {levels}')
+    for name, t in zip('DHW', target):
+        if t % (1 << (levels - 1)):
+            raise ValueError(f'block_pyramid: target {name} = {t} is not a multiple of 2^{levels - 1} for {levels} levels')
+    if stats and out_dtype == torch.float32:
+        raise ValueError('block_pyramid: stats are the exact integer sums of integer outputs; reduce float32 levels yourself')
+    off = pyramid_offsets(x.shape[1:], target, anchor)
+    pad_value = intercept if pad_value is None else pad_value
+    if is_int:
+        for name, s in (('intercept', intercept), ('pad_value', pad_value)):
+            if int(s) != s or abs(int(s)) > _PYR_SCALAR_MAX:
+                raise ValueError(f'block_pyramid: {name} of an integer source is an integer within +-2^30, got {s!r}')
+        intercept, pad_value = int(intercept), int(pad_value)
+        lo, hi = _PYR_RANGE[out_dtype] if clip is None else clip
+        if int(lo) != lo or int(hi) != hi:
+            raise ValueError(f'block_pyramid: clip bounds of an integer source are integers, got {clip!r}')
+        lo, hi = int(lo), int(hi)
+        if lo > hi or lo < _PYR_RANGE[out_dtype][0] or hi > _PYR_RANGE[out_dtype][1]:
+            raise ValueError(f'block_pyramid: clip ({lo}, {hi}) is empty or outside {out_dtype}')
+    else:
+        intercept, pad_value = float(intercept), float(pad_value)
+        lo, hi = (-math.inf, math.inf) if clip is None else (float(clip[0]), float(clip[1]))
+        if not lo <= hi:
+            raise ValueError(f'block_pyramid: clip ({lo}, {hi}) is empty')
+        if not (math.isfinite(intercept) and math.isfinite(pad_value)):
+            raise ValueError('block_pyramid: intercept and pad_value are finite')
+    n = x.shape[0]
+    if not x.is_cuda:
+        outs, st = _pyramid_numpy(x, target, off, levels, reduce, intercept, pad_value, lo, hi, out_dtype, stats)
+        return (outs, st) if stats else outs
+    outs, st = block_pyramid_launch(x, target, off, levels, reduce, intercept, pad_value, lo, hi, out_dtype, stats)
+    if stats and (n == 0 or 0 in target):      # (nothing was launched: the statistics keep their identities)
+        st = torch.tensor([0, 0, 2 ** 63 - 1, -2 ** 63], device=x.device).expand(n, levels, 4).contiguous()
+    return (outs, st) if stats else outs
