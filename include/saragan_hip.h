@@ -772,6 +772,35 @@ int sg_block_pyramid(const void* x, sg_src_dtype dt, int64_t n, int64_t sd, int6
                      int32_t clip_lo_i, int32_t clip_hi_i, float intercept_f, float pad_f, float clip_lo_f, float clip_hi_f,
                      sg_src_dtype out_dt, void* const* out, int64_t* stats, sg_stream_t st);
 
+/* ---- resampling to a common voxel spacing (csrc/resample.hip; prepare_data.py --spacing) --------------------------
+ * One launch resamples a batch of source volumes x [n, sd, sh, sw] (the source type dt: any sg_src_dtype except SG_SRC_BF16;
+ * contiguous, on the device, aligned to its element size) to y [n, od, oh, ow] of the output type out_dt (SG_SRC_U16, SG_SRC_I16
+ * or SG_SRC_F32 -- the types sg_block_pyramid takes as sources; integer sources take any of the three, f16 / f32 sources
+ * SG_SRC_F32 only), separably, through one TAP TABLE per axis that the caller built (table_ops.resample_taps: nearest,
+ * linear, a triangle antialiasing filter; a negative step flips the axis).
+ * The table of an axis with O outputs and T taps (taps_d, taps_h, taps_w: 1 .. SG_RESAMPLE_MAX_TAPS, one count per axis per
+ * launch) is a DEVICE int32 [1 + 2 T][O], tap-major: row 0 holds the `inside` flag of every output index (0: outside), rows
+ * 1 .. T the source index of tap k, rows T + 1 .. 2 T the bits of its f32 weight.
+ * Exactly, per output voxel (o_d, o_h, o_w), with (id, wd), (ih, wh), (iw, ww) the taps of its three output indices:
+ *   outside on any axis (or an empty source):  y = the fill value, stored as a value is
+ *   inner(d, h) = sum_k f64(ww[k]) * f64(x[d, h, iw[k]])      taps in table order, sequential adds from 0.0
+ *   mid(d)      = sum_j f64(wh[j]) * inner(d, ih[j])
+ *   acc         = sum_i f64(wd[i]) * mid(id[i])
+ *   a tap whose weight is exactly 0 is skipped: its voxel (row, plane) is not read and nothing is added, so a NaN behind a
+ *   zero weight does not leak
+ *   stored: SG_SRC_F32: f32(acc), one rounding;  SG_SRC_I16 / SG_SRC_U16: clamp(rint(acc), the type's range), ties to even
+ * Every product and every sum rounds on its own (no fused multiply-add).  The fill value is f64(fill_i) for integer sources and
+ * f64(fill_f) for float sources.  Weights are finite; a source index outside [0, extent) is clamped to it in the kernel, so
+ * nothing outside x is read whatever the tables hold (the Python wrapper builds and checks its tables on the host).
+ * Every output voxel has one writer; there are no atomics; every offset is 64-bit; source rows need only element alignment.
+ * SG_EINVAL before any launch: a NULL pointer with work to do; a negative extent; a tap count outside [1, 32]; an unknown dt
+ * or out_dt, SG_SRC_BF16; a float source with an integer out_dt; an extent > 2^29.  SG_EALIGN: x or y not aligned to its
+ * element size, a table not 4-byte aligned.  n == 0 or an empty output: SG_OK, nothing launched. */
+#define SG_RESAMPLE_MAX_TAPS 32
+int sg_resample_axes(const void* x, sg_src_dtype dt, int64_t n, int64_t sd, int64_t sh, int64_t sw, int64_t od, int64_t oh, int64_t ow,
+                     const int32_t* tab_d, int32_t taps_d, const int32_t* tab_h, int32_t taps_h, const int32_t* tab_w,
+                     int32_t taps_w, int32_t fill_i, float fill_f, sg_src_dtype out_dt, void* y, sg_stream_t st);
+
 /* ---- opt-in kernel timing (used by bench.py's roofline leg) ------------------------------------- */
 /* When enabled, every sg_conv3d_fwd / sg_conv3d_wgrad launch is bracketed by hipEvents on its stream.
  * sg_prof_collect synchronises those events and returns, per kind (0 = conv fwd, 1 = wgrad) and per

@@ -375,3 +375,178 @@ def block_pyramid(x, target, levels, reduce='mean', intercept=0, pad_value=None,
     if stats and (n == 0 or 0 in target):      # (nothing was launched: the statistics keep their identities)
         st = torch.tensor([0, 0, 2 ** 63 - 1, -2 ** 63], device=x.device).expand(n, levels, 4).contiguous()
     return (outs, st) if stats else outs
+
+
+# ---- resampling to a common voxel spacing: one tap table per axis, built here in f64; a separable f64 evaluation in table order
+RESAMPLE_MODES = ('nearest', 'linear', 'antialias')
+_RS_OUT_NP = {torch.uint16: 'uint16', torch.int16: 'int16', torch.float32: 'float32'}
+_RS_MAX_K = 15      # the widest antialiasing triangle: 2 * 15 + 1 = 31 taps of SG_RESAMPLE_MAX_TAPS
+
+
+def resample_taps(S, O, step, start, mode='linear'):
+    """The tap table of one axis: (inside bool [O], index int32 [O, T], weight float32 [O, T]).  Output index o sits at the source
+    coordinate c = start + o * step (numpy f64; a negative step is a flipped axis) and is inside when -0.5 <= c <= S - 0.5 (ITK's
+    buffer test).  nearest: one tap floor(c + 0.5).  linear: floor(c) and floor(c) + 1 with weights 1 - f and f.  antialias: a
+    triangle of half-width k = max(1, |step|) source voxels -- the T = floor(2 k) + 1 taps from ceil(c - k) on, weight
+    max(0, 1 - |i - c| / k) normalised to sum 1 in f64 (taps past floor(c + k) get 0); at |step| <= 1 the triangle IS the linear
+    kernel and the linear table is returned; k > 15 is a ValueError.  Indices are clamped to [0, S - 1] (the edge voxel repeats);
+    weights are rounded to f32 last."""
+    import numpy as np
+    S, O = int(S), int(O)
+    step, start = float(step), float(start)
+    if mode not in RESAMPLE_MODES:
+        raise ValueError(f'resample_taps: mode is nearest, linear or antialias, got {mode!r}')
+    if S < 1 or O < 0:
+        raise ValueError(f'resample_taps: a source extent >= 1 and an output extent >= 0, got {S} and {O}')
+    if not math.isfinite(step) or step == 0.0 or not math.isfinite(start):
+        raise ValueError(f'resample_taps: step is finite and not 0, start is finite, got {step!r} and {start!r}')
+    k = max(1.0, abs(step))
+    if mode == 'antialias':
+        if k > _RS_MAX_K:
+            raise ValueError(f'resample_taps: antialias spans |step| <= {_RS_MAX_K} source voxels, got {step!r}')
+        if k == 1.0:
+            mode = 'linear'
+    c = start + np.arange(O, dtype=np.float64) * step
+    inside = (c >= -0.5) & (c <= S - 0.5)
+    if mode == 'nearest':
+        idx = np.floor(c + 0.5)[:, None]
+        w = np.ones((O, 1), np.float64)
+    elif mode == 'linear':
+        i0 = np.floor(c)
+        f = c - i0
+        idx = np.stack([i0, i0 + 1.0], axis=1)
+        w = np.stack([1.0 - f, f], axis=1)
+    else:
+        T = int(math.floor(2.0 * k)) + 1
+        idx = np.ceil(c - k)[:, None] + np.arange(T, dtype=np.float64)[None, :]
+        w = np.maximum(0.0, 1.0 - np.abs(idx - c[:, None]) / k)
+        w = w / w.sum(axis=1, keepdims=True)
+    idx = np.clip(idx, 0, S - 1).astype(np.int32)
+    return inside, idx, w.astype(np.float32)
+
+
+def _pack_taps(taps):
+    """(inside, index, weight) -> the int32 [1 + 2 T][O] image sg_resample_axes reads (tap-major)."""
+    import numpy as np
+    inside, idx, w = taps
+    return np.ascontiguousarray(np.concatenate([inside.astype(np.int32)[None, :], idx.T, np.ascontiguousarray(w.T).view(np.int32)], axis=0))
+
+
+def _resample_store(acc, out_np):
+    import numpy as np
+    if out_np == 'float32':
+        with np.errstate(over='ignore', invalid='ignore'):
+            return acc.astype(np.float32)
+    info = np.iinfo(out_np)
+    return np.clip(np.rint(acc), info.min, info.max).astype(out_np)
+
+
+def _resample_numpy(x, taps, out_shape, fill, out_dtype):
+    """The CPU path: the kernel's definition in numpy f64, in the same order -- vectorised over voxels, looping over taps."""
+    import numpy as np
+    a = x.numpy()
+    out_np = _RS_OUT_NP[out_dtype]
+    (ins_d, id_, wd), (ins_h, ih, wh), (ins_w, iw, ww) = taps
+    od, oh, ow = out_shape
+    y = np.empty((a.shape[0], od, oh, ow), out_np)
+    filled = _resample_store(np.float64(fill), out_np)
+    inside = ins_d[:, None, None] & ins_h[None, :, None] & ins_w[None, None, :]
+    if not inside.any() or 0 in a.shape[1:]:
+        y[...] = filled
+        return torch.from_numpy(y)
+    # the source planes some inside output plane reads with a weight that is not 0
+    planes = np.unique(id_[(wd != 0) & ins_d[:, None]])
+    slot = np.zeros(a.shape[1], np.int64)
+    slot[planes] = np.arange(len(planes))
+    with np.errstate(over='ignore', invalid='ignore'):
+        for s in range(a.shape[0]):
+            mid = np.empty((len(planes), oh, ow), np.float64)
+            for p, d in enumerate(planes):
+                v = a[s, d]
+                inner = np.zeros((a.shape[2], ow), np.float64)
+                for k in range(ww.shape[1]):
+                    term = ww[:, k].astype(np.float64)[None, :] * v[:, iw[:, k]].astype(np.float64)
+                    inner = np.where((ww[:, k] != 0)[None, :], inner + term, inner)
+                m = np.zeros((oh, ow), np.float64)
+                for j in range(wh.shape[1]):
+                    term = wh[:, j].astype(np.float64)[:, None] * inner[ih[:, j], :]
+                    m = np.where((wh[:, j] != 0)[:, None], m + term, m)
+                mid[p] = m
+            acc = np.zeros((od, oh, ow), np.float64)
+            for i in range(wd.shape[1]):
+                term = wd[:, i].astype(np.float64)[:, None, None] * mid[slot[id_[:, i]]]
+                acc = np.where((wd[:, i] != 0)[:, None, None], acc + term, acc)
+            y[s] = np.where(inside, _resample_store(acc, out_np), filled)
+    return torch.from_numpy(y)
+
+
+def resample_launch(x, packed, taps_per_axis, out_shape, fill, out_dtype):
+    """One sg_resample_axes launch on checked arguments; packed: the three device tables (_pack_taps images)."""
+    lib = _lib.load()
+    n = x.shape[0]
+    y = torch.empty((n,) + tuple(out_shape), device=x.device, dtype=out_dtype)
+    is_int = not x.dtype.is_floating_point
+    with torch.cuda.device(x.device):
+        check(lib.sg_resample_axes(_ptr(x), SRC_DT[x.dtype], n, x.shape[1], x.shape[2], x.shape[3], out_shape[0], out_shape[1],
+                                   out_shape[2], _ptr(packed[0]), taps_per_axis[0], _ptr(packed[1]), taps_per_axis[1],
+                                   _ptr(packed[2]), taps_per_axis[2], int(fill) if is_int else 0, 0.0 if is_int else float(fill),
+                                   PYR_OUT_DT[out_dtype], _ptr(y), _stream()), 'sg_resample_axes')
+    return y
+
+
+def resample_volume(x, out_shape, step, start, mode='linear', fill=0, out_dtype=None):
+    """x [n, sd, sh, sw] (u8 / i8 / i16 / u16 / f16 / f32, contiguous) resampled to [n, od, oh, ow] of out_dtype (uint16, int16 or
+    float32; None: int16 for signed integer sources, uint16 for unsigned, float32 for floats, which take nothing else).  Per axis,
+    output index o reads the source coordinate start + o * step (step, start: one number per axis; a negative step flips) through
+    the taps of resample_taps(mode) (mode: one name, or one per axis); an output voxel outside the source on any axis is `fill`
+    (an integer for integer sources).  A voxel inside is the f64 sum over the d taps of wd * (the sum over the h taps of wh * (the
+    sum over the w taps of ww * x)), in table order, a tap of weight 0 skipped; then one rounding to float32, or rint (ties to
+    even) and a clamp to the integer type.  On the device that is one sg_resample_axes launch; a CPU tensor takes the same
+    definition in numpy and gives the same bits."""
+    if not torch.is_tensor(x):
+        raise TypeError(f'resample_volume: expected a tensor, got {type(x).__name__}')
+    if x.dtype not in SRC_DT:
+        raise TypeError(f'resample_volume: sources are uint8, int8, int16, uint16, float16 or float32, got {x.dtype}')
+    is_int = not x.dtype.is_floating_point
+    if out_dtype is None:
+        out_dtype = torch.float32 if not is_int else torch.uint16 if x.dtype in (torch.uint8, torch.uint16) else torch.int16
+    if out_dtype not in PYR_OUT_DT:
+        raise TypeError(f'resample_volume: out_dtype is uint16, int16 or float32, got {out_dtype}')
+    if not is_int and out_dtype != torch.float32:
+        raise TypeError(f'resample_volume: a {x.dtype} source takes out_dtype float32, got {out_dtype}')
+    if x.dim() != 4 or not x.is_contiguous():
+        raise ValueError(f'resample_volume: expected a contiguous [n, d, h, w] tensor, got {tuple(x.shape)}')
+    try:
+        out_shape = tuple(int(t) for t in out_shape)
+        step, start = tuple(float(s) for s in step), tuple(float(s) for s in start)
+    except TypeError:
+        raise ValueError('resample_volume: out_shape, step and start are one number per axis (d, h, w)')
+    if len(out_shape) != 3 or len(step) != 3 or len(start) != 3:
+        raise ValueError(f'resample_volume: out_shape, step and start are one number per axis (d, h, w), got {out_shape}, {step}, {start}')
+    if min(out_shape) < 0 or max(out_shape + tuple(x.shape[1:])) > _PYR_EXTENT_MAX:
+        raise ValueError(f'resample_volume: extents lie in [0, 2^29], got {out_shape} from {tuple(x.shape[1:])}')
+    modes = (mode,) * 3 if isinstance(mode, str) else tuple(mode)
+    if len(modes) != 3 or any(m not in RESAMPLE_MODES for m in modes):
+        raise ValueError(f'resample_volume: mode is nearest, linear or antialias (one, or one per axis), got {mode!r}')
+    if is_int:
+        if isinstance(fill, bool) or int(fill) != fill or abs(int(fill)) >= 2 ** 31:
+            raise ValueError(f'resample_volume: fill of an integer source is a 32-bit integer, got {fill!r}')
+        fill = int(fill)
+    else:
+        fill = float(fill)
+    n = x.shape[0]
+    if n == 0 or 0 in out_shape:
+        return torch.empty((n,) + out_shape, device=x.device, dtype=out_dtype)
+    # (an empty source axis has no voxel to tap: its table is all outside)
+    taps = []
+    for S, O, st, s0, m in zip(x.shape[1:], out_shape, step, start, modes):
+        if S == 0:
+            import numpy as np
+            resample_taps(1, O, st, s0, m)      # (the argument checks)
+            taps.append((np.zeros(O, bool), np.zeros((O, 1), np.int32), np.zeros((O, 1), np.float32)))
+        else:
+            taps.append(resample_taps(S, O, st, s0, m))
+    if not x.is_cuda:
+        return _resample_numpy(x, taps, out_shape, fill, out_dtype)
+    packed = [torch.from_numpy(_pack_taps(t)).to(x.device) for t in taps]
+    return resample_launch(x, packed, [t[1].shape[1] for t in taps], out_shape, fill, out_dtype)
