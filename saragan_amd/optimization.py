@@ -751,6 +751,10 @@ class StepGraph:
             else:
                 out[('max_norm', tid)] = torch.sqrt(sq).max()
         out[('gradients', tid)] = [self.store.vars[n].grad for n in names]
+        if gscale != 1.0 and ('gradients', tid) in self._wanted:
+            # unclipped, the flat buffer holds the SUM over ranks (the average is folded into the update kernel);
+            # hvd.DistributedOptimizer.compute_gradients returns the average: scaled here, only where they are fetched
+            out[('gradients', tid)] = [g * gscale for g in out[('gradients', tid)]]
         if apply and info['dist'] is not None and getattr(info['dist'], 'delta_form', False):
             # hvd.Adasum on a TF1 optimizer (parallel.AdasumReducer): local step, then the ranks' weight deltas are combined.
             # The EMA update must see the combined weights: it is left to ExtendedEMA.apply (these ranges stay unmarked).

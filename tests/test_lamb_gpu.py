@@ -61,9 +61,9 @@ def _pad_mask():
 _REF = {}
 
 
-def _reference(kind):
-    """Per step {name: (w, m, v, shadow)} in fp64, computed once per rule and shared (never modified)."""
-    if kind not in _REF:
+def _reference(kind, gscale=GSCALE):
+    """Per step {name: (w, m, v, shadow)} in fp64, computed once per rule and gradient scale and shared (never modified)."""
+    if (kind, gscale) not in _REF:
         offs, _ = _layout()
         st = _host_state()
         rule = RULES[kind](B1, B2, LAM, 1e-6)
@@ -71,14 +71,14 @@ def _reference(kind):
         sh = {k: st['ema'][o:o + n].double() for k, (o, n) in offs.items()}
         out = []
         for s in range(STEPS):
-            rule.apply(p, {k: st['g'][s][o:o + n].double() * GSCALE for k, (o, n) in offs.items()}, LR)
+            rule.apply(p, {k: st['g'][s][o:o + n].double() * gscale for k, (o, n) in offs.items()}, LR)
             for k in p:
                 sh[k] = sh[k] - (1 - EMA) * (sh[k] - p[k])
             out.append({k: (p[k].clone(), rule.m[k].clone(), rule.v[k].clone(), sh[k].clone()) for k in p})
         if kind == 'LAMB':      # the cases the segments are there for
             assert rule.ratios['net/zero_u/bias'] == 1.0 and rule.ratios['net/live/bias'] != 1.0
-        _REF[kind] = out
-    return _REF[kind]
+        _REF[kind, gscale] = out
+    return _REF[kind, gscale]
 
 
 def _make(kind, names=None):
@@ -109,13 +109,13 @@ def _snap(o, flat, ema):
     return dict(p=flat['param'].clone(), m=o.state['net/']['m'].clone(), v=o.state['net/']['v'].clone(), ema=ema.clone())
 
 
-def _run(kind, steps=STEPS, lr_dev=False, names=None):
+def _run(kind, steps=STEPS, lr_dev=False, names=None, gscale=GSCALE):
     o, flat, ema, ranges, gs = _make(kind, names)
     lr_t = torch.tensor([LR], device='cuda') if lr_dev else None
     snaps = []
     for s in range(steps):
         flat['grad'].copy_(gs[s])
-        o.apply('net/', flat, ranges, GSCALE, ema, EMA, lr_dev=lr_t)
+        o.apply('net/', flat, ranges, gscale, ema, EMA, lr_dev=lr_t)
         snaps.append(_snap(o, flat, ema))
     return o, snaps
 
@@ -152,6 +152,31 @@ def test_three_steps_match_the_fp64_rule_and_leave_the_padding(kind):
         assert (tab.nseg, tab.nblocks) == (len(SEGMENTS), len(SEGMENTS) + 3)
     else:
         assert o.t_dev is None                                             # AdamW reads only lr
+
+
+@pytest.mark.parametrize('gscale', [0.5, 1.0 / 3.0])
+@pytest.mark.parametrize('kind', KINDS)
+def test_the_gradient_scale_of_n_ranks_enters_as_g_times_gscale(kind, gscale):
+    """gscale = 1 / world (the data-parallel average folded into the update): sg_adamw_ema and the sg_lamb_moments /
+    sg_lamb_ratios / sg_lamb_update chain against the fp64 rule fed g * gscale formed in fp64 -- 1/3 is no power of two, so a
+    kernel that scaled anything but the gradient (m, v and, through u, LAMB's trust-ratio norms) would not round its way back.
+    Same segments (vector body, scalar tail, multi-block norm) and tolerances as the test above; and the gscale = 1 rule is
+    NOT within them, so the comparison can tell."""
+    offs, _ = _layout()
+    ref, unscaled = _reference(kind, gscale), _reference(kind, 1.0)
+    _, snaps = _run(kind, gscale=gscale)
+    pad = _pad_mask().cuda()
+    for s, snap in enumerate(snaps):
+        for k in ('p', 'm', 'v', 'ema'):
+            assert bool((snap[k][pad] == SENTINEL).all()), (s, k)
+        for name, (b, n) in offs.items():
+            for key, want in zip(('p', 'm', 'v', 'ema'), ref[s][name]):
+                np.testing.assert_allclose(snap[key][b:b + n].double().cpu().numpy(), want.numpy(), rtol=1e-5, atol=1e-6,
+                                           err_msg=f'{kind} gscale {gscale} step {s} {name} {key}')
+    b, n = offs['net/big/weight']
+    for key, j in (('m', 1), ('v', 2)):
+        got, other = snaps[0][key][b:b + n].double().cpu(), unscaled[0]['net/big/weight'][j]
+        assert bool(((got - other).abs() > 1e-6 + 1e-5 * other.abs()).any()), key
 
 
 @pytest.mark.parametrize('kind', KINDS)
