@@ -1763,10 +1763,14 @@ static int launch_wgrad3(WgradArgs& a, const sg_conv_shape* s, hipStream_t st, b
   if (lds > 160 * 1024) return SG_OK;
   a.tap0 = 0; a.taps_blk = a.taps;
   a.nslab = 2 * gx;      // (both wave groups of a block keep sums of their own)
-  // the lean variant: 3x3x3 without fused up-sampling, whole 32-wide rows, one sample of either tensor below 2 GiB
-  const bool lean = KD == 3 && KH == 3 && KW == 3 && g.HH == 6 && g.HW == 34 && g.HD == 4 && a.plane_rows == 208 &&
+  // the lean variant: 3x3x3 without fused up-sampling, whole 32-wide rows.  Its buffer resources hold (int) sample BYTES and treat
+  // offsets from 2^31 as dead, so a sample of x, dy or the mask words stays below 2^31 bytes (the guard above counts elements).
+  // (A 16-wide level that does not fit declines the route below: at w = 16 that needs d h >= 2^20 at 64 channels.)
+  const int64_t svox = (int64_t)s->d * s->h * s->w;
+  const bool fits = svox * (int64_t)(s->cin > s->cout ? s->cin : s->cout) * 2 < (1ll << 31) && svox * a.coT * 4 < (1ll << 31);
+  const bool lean = KD == 3 && KH == 3 && KW == 3 && g.HH == 6 && g.HW == 34 && g.HD == 4 && a.plane_rows == 208 && fits &&
                     s->w % 32 == 0 && !sg_cfg().wgrad_no_lean && (!g.ups || ((s->d | s->h | s->w) & 1) == 0);
-  const bool lean16 = w16 && g.HH == 10 && g.HW == 18 && g.HD == 4 && (!g.ups || ((s->d | s->h | s->w) & 1) == 0);
+  const bool lean16 = w16 && fits && g.HH == 10 && g.HW == 18 && g.HD == 4 && (!g.ups || ((s->d | s->h | s->w) & 1) == 0);
   if (w16 && !lean16) return SG_OK;
   if (lean16 || lean) a.nslab = gx;                   // (the lean kernels add their two groups' sums before they leave the block)
   if (lean) lds += 12288;                             // (+ the lean kernels' image of ones, behind the staging buffers)
