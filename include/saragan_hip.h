@@ -801,6 +801,36 @@ int sg_resample_axes(const void* x, sg_src_dtype dt, int64_t n, int64_t sd, int6
                      const int32_t* tab_d, int32_t taps_d, const int32_t* tab_h, int32_t taps_h, const int32_t* tab_w,
                      int32_t taps_w, int32_t fill_i, float fill_f, sg_src_dtype out_dt, void* y, sg_stream_t st);
 
+/* ---- typed volumes from the generator's output (csrc/export.hip; generate.py) ------------------------------------
+ * The mirror image of sg_gather_rows: one pass reads a batch x [n, c, d, h, w] (the source type dt: SG_SRC_F32, SG_SRC_BF16 or
+ * SG_SRC_F16; on the device, aligned to its element size; channels_last == 0: NCDHW-contiguous, != 0: the memory of NDHWC -- with
+ * c == 1 the two are the same memory) once and writes out [n, c, d, h, w], NCDHW-contiguous, of the output type out_dt (SG_SRC_I16,
+ * SG_SRC_U16, SG_SRC_U8 or SG_SRC_F32); a channels-last source with c > 1 is transposed on the way.  Per element, in f32 and exactly:
+ *   t      = x * scale + shift                 two correctly rounded operations, never fused: numpy's x * np.float32(scale) +
+ *                                              np.float32(shift) (scale = stddev, shift = mean undoes the training normalisation)
+ *   nan    = t is NaN;  below = t < lo;  above = t > hi        float comparisons, made before any conversion; +-inf saturate
+ *   u      = nan or below ? lo : above ? hi : t                 (min(max(t, lo), hi), a zero keeping its own sign)
+ *   stored = T(trunc(u))                       integer T, SG_ROUND_TRUNC: numpy's .astype, what (np.clip(x, a, b) * s).astype(T) stores
+ *            T(rint(u))                        integer T, SG_ROUND_RINT: ties to even, as sg_resample_axes stores
+ *            nan ? the quiet NaN 0x7FC00000 : u                 SG_SRC_F32 (rounding is checked and not used)
+ * For an integer T lo and hi are integers inside T's range, so no conversion can overflow; for SG_SRC_F32 they may be infinite.
+ * stats (may be NULL): DEVICE int64 [n][7] = the sum, the sum of squares, the minimum and the maximum of sample i's STORED values
+ * (integer T; four zeros for SG_SRC_F32), then the numbers of its below, above and nan elements.  Set to their identities on the
+ * stream first, then accumulated with integer atomics, one per block, row and statistic after a reduction per wave and per block:
+ * exact, independent of the order, two calls give the same bits.  No output element has two writers.  Every offset is 64-bit:
+ * n * c * d * h * w may pass 2^31.  Whole 16-byte loads and stores when the source is one contiguous row per sample (NCDHW, or
+ * c == 1), c * d * h * w is a multiple of the 16, 8 or 4 elements that make 16 bytes of the narrower type, and x and out reach
+ * a 16-byte boundary after the same number of elements (those, and as many at each row's end, go one by one); an element path
+ * otherwise -- chosen per launch.
+ * SG_EINVAL before any launch: a NULL pointer with work to do; n, d, h, w < 0 or c < 1; an unknown dt, out_dt or rounding, or a dt
+ * / out_dt outside the lists above; scale not finite; lo > hi or a NaN bound; for an integer T a bound that is not an integer or
+ * lies outside T.  SG_EALIGN: x or out not aligned to its element size, stats not 8-byte aligned.  n == 0 or an empty volume:
+ * SG_OK, nothing launched. */
+enum { SG_ROUND_TRUNC = 0, SG_ROUND_RINT = 1 };
+int sg_store_volumes(const void* x, sg_src_dtype dt, int32_t channels_last, int64_t n, int64_t c, int64_t d, int64_t h, int64_t w,
+                     float scale, float shift, float lo, float hi, int32_t rounding, sg_src_dtype out_dt, void* out, int64_t* stats,
+                     sg_stream_t st);
+
 /* ---- opt-in kernel timing (used by bench.py's roofline leg) ------------------------------------- */
 /* When enabled, every sg_conv3d_fwd / sg_conv3d_wgrad launch is bracketed by hipEvents on its stream.
  * sg_prof_collect synchronises those events and returns, per kind (0 = conv fwd, 1 = wgrad) and per

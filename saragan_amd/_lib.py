@@ -28,6 +28,8 @@ SG_PYR_MEAN, SG_PYR_MAX = 0, 1
 SG_PYRAMID_LEVELS_PER_LAUNCH = 6
 # sg_resample_axes: the most taps an axis's table holds per output index
 SG_RESAMPLE_MAX_TAPS = 32
+# sg_store_volumes roundings
+SG_ROUND_TRUNC, SG_ROUND_RINT = 0, 1
 
 
 class ConvShape(C.Structure):
@@ -176,6 +178,7 @@ SIGNATURES = {
                                    _i32, _i32, _f, _f, _f, _f, C.c_int, C.POINTER(_p), _p, _p]),
     'sg_resample_axes': (C.c_int, [_p, C.c_int, _i64, _i64, _i64, _i64, _i64, _i64, _i64, _p, _i32, _p, _i32, _p, _i32, _i32, _f, C.c_int,
                                    _p, _p]),
+    'sg_store_volumes': (C.c_int, [_p, C.c_int, _i32, _i64, _i64, _i64, _i64, _i64, _f, _f, _f, _f, _i32, C.c_int, _p, _p, _p]),
     'sg_prof_enable': (C.c_int, [C.c_int]),
     'sg_prof_enabled': (C.c_int, []),
     'sg_prof_collect': (C.c_int, [C.POINTER(ProfEntry), _i32, C.POINTER(_i32)]),

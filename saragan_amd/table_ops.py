@@ -1,6 +1,7 @@
 """Reads of typed device tables: batches gathered from a resident dataset (dataset.ResidentLoader),
-voxel-intensity histograms (metrics/intensity_metrics.py), rendered views (preview.py) and the
-dataset pyramid of full-size volumes (prepare_data.py).  Re-exported by functional."""
+voxel-intensity histograms (metrics/intensity_metrics.py), rendered views (preview.py), the
+dataset pyramid of full-size volumes (prepare_data.py) and its resampler -- and the one write:
+typed volumes stored from the generator's output (generate.py).  Re-exported by functional."""
 import math
 
 import torch
@@ -550,3 +551,96 @@ def resample_volume(x, out_shape, step, start, mode='linear', fill=0, out_dtype=
         return _resample_numpy(x, taps, out_shape, fill, out_dtype)
     packed = [torch.from_numpy(_pack_taps(t)).to(x.device) for t in taps]
     return resample_launch(x, packed, [t[1].shape[1] for t in taps], out_shape, fill, out_dtype)
+
+
+# ---- typed volumes from the generator's output: de-normalise, clip, round, cast, per-sample statistics
+STORE_SRC_DT = {torch.float32: _lib.SG_SRC_F32, torch.bfloat16: _lib.SG_SRC_BF16, torch.float16: _lib.SG_SRC_F16}
+STORE_OUT_DT = {torch.int16: _lib.SG_SRC_I16, torch.uint16: _lib.SG_SRC_U16, torch.uint8: _lib.SG_SRC_U8, torch.float32: _lib.SG_SRC_F32}
+STORE_ROUNDINGS = {'trunc': _lib.SG_ROUND_TRUNC, 'rint': _lib.SG_ROUND_RINT}
+_STORE_RANGE = {torch.int16: (-32768, 32767), torch.uint16: (0, 65535), torch.uint8: (0, 255)}
+_STORE_NP = {torch.int16: 'int16', torch.uint16: 'uint16', torch.uint8: 'uint8', torch.float32: 'float32'}
+STORE_DEFINITION = ('t = f32(x) * f32(scale) + f32(shift), two roundings; nan = isnan(t), below = t < lo, above = t > hi; '
+                    'u = lo if nan or below, hi if above, else t; stored = T(trunc(u)) or T(rint(u), ties to even) for an integer T, '
+                    'NaN if nan else u for float32')
+
+
+def _store_numpy(x, out_dtype, scale, shift, lo, hi, rounding, want_stats):
+    """The CPU path: the kernel's definition in numpy, operation by operation."""
+    import numpy as np
+    a = x.float().numpy().astype(np.float32, copy=False)      # [n, c, d, h, w] by index, whatever the strides (every source converts exactly)
+    n = a.shape[0]
+    flo, fhi = np.float32(lo), np.float32(hi)
+    with np.errstate(over='ignore', invalid='ignore'):
+        t = a * np.float32(scale) + np.float32(shift)
+        nan, below, above = np.isnan(t), t < flo, t > fhi
+    u = np.where(nan | below, flo, np.where(above, fhi, t)).astype(np.float32)
+    st = np.zeros((n, 7), np.int64)
+    if out_dtype == torch.float32:
+        stored = np.where(nan, np.float32(np.nan), u).astype(np.float32)
+    else:
+        stored = (np.rint(u) if rounding == 'rint' else np.trunc(u)).astype(_STORE_NP[out_dtype])
+        if n and stored[0].size:
+            s = stored.reshape(n, -1).astype(np.int64)
+            st[:, :4] = np.stack([s.sum(1), (s * s).sum(1), s.min(1), s.max(1)], axis=1)
+    st[:, 4:] = np.stack([m.sum(axis=(1, 2, 3, 4)) for m in (below, above, nan)], axis=1)
+    return torch.from_numpy(np.ascontiguousarray(stored)), (torch.from_numpy(st) if want_stats else None)
+
+
+def store_volumes(x, out_dtype, scale=1.0, shift=0.0, clip=None, rounding='trunc', stats=False, out=None):
+    """A batch x [n, c, d, h, w] (f32 / bf16 / f16; contiguous, or channels_last_3d: transposed on the way) mapped back to data units
+    and stored as a contiguous [n, c, d, h, w] of out_dtype (int16, uint16, uint8 or float32), one pass (sg_store_volumes).  Per
+    element, exactly: t = x * scale + shift in two correctly rounded f32 operations -- numpy's x * np.float32(scale) +
+    np.float32(shift); nan, below, above = isnan(t), t < lo, t > hi with clip = (lo, hi) (None: the type's range, +-inf for
+    float32; integers for an integer type); u = lo where nan or below, hi where above, else t; stored = T(trunc(u)) -- the bits of
+    (np.clip(x, a, b) * s).astype(T) -- or T(rint(u)), ties to even; float32: NaN where nan, else u.  stats=True: (out, int64
+    [n, 7]) = the sum, sum of squares, minimum and maximum of every sample's stored values (zeros for float32), then its numbers
+    of below, above and nan elements: integer sums, two calls give the same bits.  out: a contiguous buffer of the result's
+    shape and type on x's device to write into.  A CPU tensor takes the same definition in numpy and gives the same bits."""
+    if not torch.is_tensor(x):
+        raise TypeError(f'store_volumes: expected a tensor, got {type(x).__name__}')
+    if x.dtype not in STORE_SRC_DT:
+        raise TypeError(f'store_volumes: sources are float32, bfloat16 or float16, got {x.dtype}')
+    if out_dtype not in STORE_OUT_DT:
+        raise TypeError(f'store_volumes: out_dtype is int16, uint16, uint8 or float32, got {out_dtype}')
+    if x.dim() != 5:
+        raise ValueError(f'store_volumes: expected [n, c, d, h, w], got {tuple(x.shape)}')
+    n, c, d, h, w = x.shape
+    if c < 1:
+        raise ValueError(f'store_volumes: expected at least one channel, got {tuple(x.shape)}')
+    channels_last = not x.is_contiguous()
+    if channels_last and not x.is_contiguous(memory_format=torch.channels_last_3d):
+        raise ValueError('store_volumes: expected a contiguous or channels_last_3d tensor')
+    if rounding not in STORE_ROUNDINGS:
+        raise ValueError(f'store_volumes: rounding is trunc or rint, got {rounding!r}')
+    if not math.isfinite(float(scale)):
+        raise ValueError(f'store_volumes: scale {scale} is not finite')
+    if clip is not None and len(clip) != 2:
+        raise ValueError(f'store_volumes: clip is (lo, hi), got {clip!r}')
+    if out_dtype == torch.float32:
+        lo, hi = (-math.inf, math.inf) if clip is None else (float(clip[0]), float(clip[1]))
+        if not lo <= hi:
+            raise ValueError(f'store_volumes: clip ({lo}, {hi}) is empty')
+    else:
+        lo, hi = _STORE_RANGE[out_dtype] if clip is None else clip
+        if isinstance(lo, bool) or isinstance(hi, bool) or not (math.isfinite(lo) and math.isfinite(hi)) or int(lo) != lo or int(hi) != hi:
+            raise ValueError(f'store_volumes: clip bounds of an integer out_dtype are integers, got {clip!r}')
+        lo, hi = int(lo), int(hi)
+        if lo > hi or lo < _STORE_RANGE[out_dtype][0] or hi > _STORE_RANGE[out_dtype][1]:
+            raise ValueError(f'store_volumes: clip ({lo}, {hi}) is empty or outside {out_dtype}')
+    shape = (n, c, d, h, w)
+    if out is not None and (not torch.is_tensor(out) or tuple(out.shape) != shape or out.dtype != out_dtype or out.device != x.device
+                            or not out.is_contiguous()):
+        raise ValueError(f'store_volumes: out must be a contiguous {out_dtype} {shape} tensor on {x.device}')
+    if not x.is_cuda:
+        res, st = _store_numpy(x, out_dtype, scale, shift, lo, hi, rounding, stats)
+        res = res if out is None else out.copy_(res)
+        return (res, st) if stats else res
+    lib = _lib.load()
+    if out is None:
+        out = torch.empty(shape, device=x.device, dtype=out_dtype)
+    st = torch.zeros((n, 7), device=x.device, dtype=torch.int64) if stats else None      # (nothing is launched for an empty batch)
+    with torch.cuda.device(x.device):
+        check(lib.sg_store_volumes(_ptr(x), STORE_SRC_DT[x.dtype], 1 if channels_last else 0, n, c, d, h, w, float(scale), float(shift),
+                                   float(lo), float(hi), STORE_ROUNDINGS[rounding], STORE_OUT_DT[out_dtype], _ptr(out), _ptr(st),
+                                   _stream()), 'sg_store_volumes')
+    return (out, st) if stats else out
