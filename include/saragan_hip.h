@@ -831,6 +831,38 @@ int sg_store_volumes(const void* x, sg_src_dtype dt, int32_t channels_last, int6
                      float scale, float shift, float lo, float hi, int32_t rounding, sg_src_dtype out_dt, void* out, int64_t* stats,
                      sg_stream_t st);
 
+/* ---- exact squared distances between typed integer rows, and the running k nearest (csrc/sqdist_exact.hip; DESIGN.md 4.12;
+ * metrics/memorisation.py) -------------------------------------------------------------------------------------------------------
+ * q [mq, v] and r [mr, v] of the source type dt (SG_SRC_U8, SG_SRC_I8, SG_SRC_I16 or SG_SRC_U16), row-major, contiguous, on the
+ * device, aligned to their element size; out: DEVICE int64 [mq, mr]:
+ *   out[i][j] = sum over e of (q[i][e] - r[j][e])^2,  exactly (v < 2^31 keeps it inside int64).
+ * A 16-bit voxel s (u16: minus 32768, a common shift) splits into the signed bytes h = s >> 8 and l = (s & 255) - 128;
+ * t = 256 h + l = s - 128, and out = |tq|^2 + |tr|^2 - 2 tq.tr with tq.tr = 65536 h.h + 256 (h.l + l.h) + l.l: four dot products
+ * on v_mfma_i32_16x16x64_i8 (8-bit types: one, u8 minus 128), accumulated in i32 over at most sg_sqdist_exact_chunk() voxels
+ * (|product| <= 2^14, two products per voxel in the cross sum: 2^29 at most) and then in i64; the row norms and the combination
+ * are i64.  K is split over the grid; the splits' integer partial tiles meet in the workspace and are added by a last kernel: no
+ * atomics, exact, independent of the split -- two calls give the same bits.  r == q with mr == mq is the symmetric case: only
+ * tiles on and above the diagonal are computed, out[j][i] == out[i][j] and the diagonal is 0.  mq, mr need not be multiples of
+ * the 64-row tile nor v of anything; rows past the end and voxels past a split's end are staged as zeros, never read.  16-byte
+ * loads where a row's bytes are 16-byte aligned, element loads elsewhere (chosen per 16 bytes, so a row of an odd v or a view
+ * that starts mid-buffer only needs element alignment).  Every offset is 64-bit: mr * v may pass 2^32 bytes.
+ * workspace: sg_sqdist_exact_workspace(mq, mr, v) bytes (covers the symmetric call of the same sizes), 8-byte aligned.
+ * SG_EINVAL before any launch: a NULL pointer, mq < 1, mr < 1, v < 1, v >= 2^31, any other dt.  SG_EWORKSPACE: the workspace is
+ * too small.  SG_EALIGN: q, r not aligned to their element size, or out, workspace not 8-byte aligned. */
+int32_t sg_sqdist_exact_chunk(void);      /* the longest i32 accumulation, in elements of v */
+size_t sg_sqdist_exact_workspace(int32_t mq, int32_t mr, int64_t v);
+int sg_sqdist_exact(const void* q, const void* r, sg_src_dtype dt, int32_t mq, int32_t mr, int64_t v, int64_t* out, void* workspace,
+                    size_t workspace_bytes, sg_stream_t st);
+/* best_d, best_id: DEVICE int64 [mq, k], every row sorted ascending by (distance, id); the caller starts them at INT64_MAX / -1
+ * (an entry with id -1 is empty).  The call merges into them the mr candidates of every row of d [mq, mr] (DEVICE int64), whose
+ * ids are r_base + j.  q_ids (may be NULL): DEVICE int64 [mq]; the candidate whose id equals q_ids[i] is skipped in row i
+ * (leave-one-out for a set against itself).  Equal distances go to the lower id, so the result does not depend on how the
+ * reference set was cut into calls.  One wave per row and one writer per row: no atomics.
+ * SG_EINVAL before any launch: a NULL d, best_d or best_id; mq < 1, mr < 1, r_base < 0; k outside 1 .. 16.  SG_EALIGN: a pointer
+ * not 8-byte aligned. */
+int sg_topk_merge(const int64_t* d, int32_t mq, int32_t mr, int64_t r_base, const int64_t* q_ids, int32_t k, int64_t* best_d,
+                  int64_t* best_id, sg_stream_t st);
+
 /* ---- opt-in kernel timing (used by bench.py's roofline leg) ------------------------------------- */
 /* When enabled, every sg_conv3d_fwd / sg_conv3d_wgrad launch is bracketed by hipEvents on its stream.
  * sg_prof_collect synchronises those events and returns, per kind (0 = conv fwd, 1 = wgrad) and per

@@ -179,6 +179,10 @@ SIGNATURES = {
     'sg_resample_axes': (C.c_int, [_p, C.c_int, _i64, _i64, _i64, _i64, _i64, _i64, _i64, _p, _i32, _p, _i32, _p, _i32, _i32, _f, C.c_int,
                                    _p, _p]),
     'sg_store_volumes': (C.c_int, [_p, C.c_int, _i32, _i64, _i64, _i64, _i64, _i64, _f, _f, _f, _f, _i32, C.c_int, _p, _p, _p]),
+    'sg_sqdist_exact_chunk': (_i32, []),
+    'sg_sqdist_exact_workspace': (_sz, [_i32, _i32, _i64]),
+    'sg_sqdist_exact': (C.c_int, [_p, _p, C.c_int, _i32, _i32, _i64, _p, _p, _sz, _p]),
+    'sg_topk_merge': (C.c_int, [_p, _i32, _i32, _i64, _p, _i32, _p, _p, _p]),
     'sg_prof_enable': (C.c_int, [C.c_int]),
     'sg_prof_enabled': (C.c_int, []),
     'sg_prof_collect': (C.c_int, [C.POINTER(ProfEntry), _i32, C.POINTER(_i32)]),

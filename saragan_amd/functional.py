@@ -1326,4 +1326,5 @@ from .spectral import (SPECTRAL_MAX_BLOCKS, SPECTRAL_MIN_ROWS, SpectralTable, sp
 from .table_ops import HIST_DT as _HIST_DT, SRC_DT as _SRC_DT, check_positions, gather_rows, intensity_hist, render_view  # noqa: E402,F401
 from .table_ops import block_pyramid, pyramid_offsets, resample_taps, resample_volume  # noqa: E402,F401
 from .table_ops import STORE_DEFINITION, store_volumes  # noqa: E402,F401
+from .table_ops import nearest_rows, sqdist_exact  # noqa: E402,F401
 

@@ -1,7 +1,9 @@
 """Reads of typed device tables: batches gathered from a resident dataset (dataset.ResidentLoader),
 voxel-intensity histograms (metrics/intensity_metrics.py), rendered views (preview.py), the
 dataset pyramid of full-size volumes (prepare_data.py) and its resampler -- and the one write:
-typed volumes stored from the generator's output (generate.py).  Re-exported by functional."""
+typed volumes stored from the generator's output (generate.py).  Also the exact squared distances between typed
+integer rows and the running k nearest of the memorisation audit (metrics/memorisation.py).  Re-exported by
+functional."""
 import math
 
 import torch
@@ -644,3 +646,98 @@ def store_volumes(x, out_dtype, scale=1.0, shift=0.0, clip=None, rounding='trunc
                                    float(lo), float(hi), STORE_ROUNDINGS[rounding], STORE_OUT_DT[out_dtype], _ptr(out), _ptr(st),
                                    _stream()), 'sg_store_volumes')
     return (out, st) if stats else out
+
+
+# ---- exact squared distances between typed integer rows, and the running k nearest (metrics/memorisation.py)
+SQDIST_DT = {torch.uint8: _lib.SG_SRC_U8, torch.int8: _lib.SG_SRC_I8, torch.int16: _lib.SG_SRC_I16, torch.uint16: _lib.SG_SRC_U16}
+TOPK_MAX = 16
+_I64_MAX = 2 ** 63 - 1
+
+
+def _sqdist_rows(x, name):
+    if not torch.is_tensor(x):
+        raise TypeError(f'sqdist_exact: expected a tensor for {name}, got {type(x).__name__}')
+    if x.dtype not in SQDIST_DT:
+        raise TypeError(f'sqdist_exact: rows are uint8, int8, int16 or uint16, got {x.dtype} for {name}')
+    if x.dim() < 1 or x.shape[0] < 1 or not x.is_contiguous():
+        raise ValueError(f'sqdist_exact: expected a contiguous [m, ...] tensor with m >= 1 for {name}, got {tuple(x.shape)}')
+    x = x.view(x.shape[0], -1)
+    if not 1 <= x.shape[1] < 2 ** 31:
+        raise ValueError(f'sqdist_exact: rows of 1 .. 2^31 - 1 elements, got {x.shape[1]} for {name}')
+    return x
+
+
+def sqdist_exact(q, r=None):
+    """int64 [mq, mr]: out[i][j] = sum_e (q[i][e] - r[j][e])^2, exactly, for q [mq, ...] and r [mr, ...] of one integer type (u8 / i8 /
+    i16 / u16; contiguous, flattened per row).  r=None: q against itself -- the upper triangle computed, mirrored, a zero diagonal.
+    On the device: sg_sqdist_exact, byte-split int8 MFMAs with integer accumulation, the same bits on every call.  A CPU tensor
+    takes numpy int64 arithmetic and gives the same numbers."""
+    sym = r is None or r is q
+    q = _sqdist_rows(q, 'q')
+    r = q if sym else _sqdist_rows(r, 'r')
+    if r.dtype != q.dtype:
+        raise TypeError(f'sqdist_exact: q is {q.dtype} and r is {r.dtype}')
+    if r.shape[1] != q.shape[1]:
+        raise ValueError(f'sqdist_exact: {q.shape[1]} and {r.shape[1]} elements per row')
+    if r.device != q.device:
+        raise ValueError('sqdist_exact: q and r on different devices')
+    mq, mr, v = q.shape[0], r.shape[0], q.shape[1]
+    if not q.is_cuda:
+        import numpy as np
+        b = r.numpy().astype(np.int64)
+        a = b if sym else q.numpy().astype(np.int64)
+        res = np.empty((mq, mr), np.int64)
+        for i in range(mq):
+            diff = b - a[i]
+            res[i] = np.einsum('jv,jv->j', diff, diff)
+        return torch.from_numpy(res)
+    lib = _lib.load()
+    with torch.cuda.device(q.device):
+        nbytes = lib.sg_sqdist_exact_workspace(mq, mr, v)
+        ws = torch.empty(nbytes, dtype=torch.uint8, device=q.device)
+        out = torch.empty((mq, mr), dtype=torch.int64, device=q.device)
+        check(lib.sg_sqdist_exact(_ptr(q), _ptr(r), SQDIST_DT[q.dtype], mq, mr, v, _ptr(out), _ptr(ws), nbytes, _stream()),
+              'sg_sqdist_exact')
+    return out
+
+
+def nearest_rows(d, k, r_base=0, q_ids=None, best=None):
+    """(best_d, best_id), int64 [mq, k]: per row of d [mq, mr] (int64 distances to the candidates r_base .. r_base + mr - 1) the k
+    nearest so far, ascending by (distance, id) -- equal distances go to the lower id, so cutting the candidates into calls
+    differently changes nothing.  best: the pair an earlier call returned, merged into in place; None: a fresh pair, INT64_MAX / -1
+    (an entry that stays so is empty: fewer than k candidates).  q_ids: int64 [mq]; row i skips the candidate whose id is
+    q_ids[i] (leave-one-out of a set against itself).  On the device one sg_topk_merge launch; a CPU tensor takes numpy."""
+    if not torch.is_tensor(d) or d.dtype != torch.int64 or d.dim() != 2 or d.shape[0] < 1 or d.shape[1] < 1 or not d.is_contiguous():
+        raise ValueError('nearest_rows: d is a contiguous int64 [mq, mr] tensor with mq, mr >= 1')
+    k, r_base = int(k), int(r_base)
+    if not 1 <= k <= TOPK_MAX:
+        raise ValueError(f'nearest_rows: k is 1 .. {TOPK_MAX}, got {k}')
+    if r_base < 0:
+        raise ValueError(f'nearest_rows: r_base {r_base} < 0')
+    mq, mr = d.shape
+    if q_ids is not None and (not torch.is_tensor(q_ids) or q_ids.dtype != torch.int64 or tuple(q_ids.shape) != (mq,)
+                              or q_ids.device != d.device or not q_ids.is_contiguous()):
+        raise ValueError(f'nearest_rows: q_ids is a contiguous int64 [{mq}] tensor on {d.device}')
+    if best is None:
+        best = (torch.full((mq, k), _I64_MAX, dtype=torch.int64, device=d.device),
+                torch.full((mq, k), -1, dtype=torch.int64, device=d.device))
+    best_d, best_id = best
+    for b in (best_d, best_id):
+        if not torch.is_tensor(b) or b.dtype != torch.int64 or tuple(b.shape) != (mq, k) or b.device != d.device or not b.is_contiguous():
+            raise ValueError(f'nearest_rows: best is a pair of contiguous int64 [{mq}, {k}] tensors on {d.device}')
+    if not d.is_cuda:
+        import numpy as np
+        ids = np.broadcast_to(np.arange(r_base, r_base + mr, dtype=np.int64), (mq, mr))
+        cd, ci = np.concatenate([best_d.numpy(), d.numpy()], axis=1), np.concatenate([best_id.numpy(), ids], axis=1)
+        if q_ids is not None:
+            own = np.concatenate([np.zeros((mq, k), bool), ids == q_ids.numpy()[:, None]], axis=1)
+            cd, ci = np.where(own, _I64_MAX, cd), np.where(own, -1, ci)
+        empty = ci < 0
+        for i in range(mq):
+            order = np.lexsort((ci[i], cd[i], empty[i]))[:k]      # the empty entries last, then by (distance, id)
+            best_d[i], best_id[i] = torch.from_numpy(cd[i][order]), torch.from_numpy(ci[i][order])
+        return best_d, best_id
+    lib = _lib.load()
+    with torch.cuda.device(d.device):
+        check(lib.sg_topk_merge(_ptr(d), mq, mr, r_base, _ptr(q_ids), k, _ptr(best_d), _ptr(best_id), _stream()), 'sg_topk_merge')
+    return best_d, best_id
