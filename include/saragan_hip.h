@@ -863,6 +863,42 @@ int sg_sqdist_exact(const void* q, const void* r, sg_src_dtype dt, int32_t mq, i
 int sg_topk_merge(const int64_t* d, int32_t mq, int32_t mr, int64_t r_base, const int64_t* q_ids, int32_t k, int64_t* best_d,
                   int64_t* best_id, sg_stream_t st);
 
+/* ---- projection of volumes onto the generator (csrc/project.hip; project.py) -----------------------------------------
+ * sg_multiscale_residual: the multi-scale residual loss between y [n, c, d, h, w] (ydt: SG_SRC_F32, SG_SRC_BF16 or SG_SRC_F16;
+ * channels_last as in sg_store_volumes) and the rows idx[i] (DEVICE int32 [n]; repeats allowed) of table [rows, c, d, h, w]
+ * (tdt: one of sg_gather_rows' six types, NCDHW), with its gradient grad (y's type and memory format).  Per sample, exactly:
+ *   t = (f32(x) - mean) / stddev, two roundings as sg_gather_rows;  r = f32(y) - t, one rounding;
+ *   S_0 = f64(r), S_l(B) = the sum of the eight children of the cube B of edge 2^l: the w pairs, then the h pairs, then the d pair;
+ *   m_l = S_l * 8^-l;  Q_l = m_l^2 carried up the same tree to the edge-8 cubes that tile the volume from its origin (children
+ *   outside count as +0); the cubes are added along w, those sums along h, those over (channel, d) in index order, each sum
+ *   sequential from its first element;  terms[i][l] = total / N_l, N_l = c d h w / 8^l (DEVICE f64 [n][levels]);
+ *   loss[i] = f32(lambda[0] terms[0] + lambda[1] terms[1] + ...) in f64 and this order (lambda: DEVICE f32 [levels]);
+ *   grad[v] = k[0] r + (k[1] m_1 + (k[2] m_2 + k[3] m_3)) in f64 (k: HOST f64 [levels], read before the call returns; the caller
+ *   gives k[l] = lambda[l] * (2 / N_l) / 8^l), rounded once to y's type.
+ * Two calls give the same bits.  d, h and w are multiples of 2^(levels - 1).  A position outside [0, rows) is not addressed: that
+ * sample's loss, terms and gradients are NaN.  workspace: DEVICE, sg_multiscale_residual_workspace bytes, 8-byte aligned; its
+ * contents are scratch.  Two launches (the pass, and one block per sample that adds the cubes); 64-bit offsets throughout.
+ * SG_EUNSUPPORTED: levels above sg_multiscale_residual_max_levels() (4: the cube a wave reduces in registers).  SG_EINVAL: a
+ * NULL pointer with work to do, bad extents or types, levels < 1, extents that are no multiple of 2^(levels - 1), a workspace that
+ * is too small.  SG_EALIGN: a pointer not aligned to its element size.  n == 0: SG_OK, nothing launched. */
+int32_t sg_multiscale_residual_max_levels(void);
+size_t sg_multiscale_residual_workspace(int64_t n, int64_t c, int64_t d, int64_t h, int64_t w, int32_t levels);
+int sg_multiscale_residual(const void* y, sg_src_dtype ydt, int32_t channels_last, const void* table, sg_src_dtype tdt, int64_t rows,
+                           const int32_t* idx, int64_t n, int64_t c, int64_t d, int64_t h, int64_t w, float mean, float stddev,
+                           int32_t levels, const float* lambda, const double* k, void* grad, double* terms, float* loss,
+                           void* workspace, size_t workspace_bytes, sg_stream_t st);
+/* sg_latent_step: one wave per row i of z [n, L] (all DEVICE f32 but best_step, int32 [n]), in place, in this order:
+ *   if loss[i] < best_loss[i] (never for a NaN; an equal loss keeps the earlier one): best_loss[i] = loss[i], z_best[i] = z[i],
+ *   best_step[i] = step;  then, unless lr == 0 (the scoring launch: nothing else moves), Adam in f32, every operation rounded on
+ *   its own:  m = b1 m + (1 - b1) g;  v = b2 v + ((1 - b2) g) g;  z = z - (lr (m / c1)) / (sqrt(v / c2) + eps), c_j = f32(1 -
+ *   pow(f64(b_j), step)) computed on the host;  then, with sphere != 0, z *= sqrt(L) / sqrt(s) in f64, rounded to f32, where s is
+ *   the f64 sum of z_k^2: 64 partial sums over k = j, j + 64, ... in increasing k, then added pairwise 32, 16, ..., 1 apart
+ *   (a row whose s is 0, NaN or infinite is left alone).  step >= 1.  SG_EINVAL: NULL pointers with work to do, L < 1, step < 1,
+ *   betas outside [0, 1), eps <= 0, lr < 0 or NaN.  SG_EALIGN: a pointer not 4-byte aligned. */
+int sg_latent_step(float* z, float* m, float* v, const float* grad_z, const float* loss, float* best_loss, float* z_best,
+                   int32_t* best_step, int64_t n, int64_t L, float lr, float beta1, float beta2, float eps, int32_t step,
+                   int32_t sphere, sg_stream_t st);
+
 /* ---- opt-in kernel timing (used by bench.py's roofline leg) ------------------------------------- */
 /* When enabled, every sg_conv3d_fwd / sg_conv3d_wgrad launch is bracketed by hipEvents on its stream.
  * sg_prof_collect synchronises those events and returns, per kind (0 = conv fwd, 1 = wgrad) and per

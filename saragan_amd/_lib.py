@@ -30,6 +30,8 @@ SG_PYRAMID_LEVELS_PER_LAUNCH = 6
 SG_RESAMPLE_MAX_TAPS = 32
 # sg_store_volumes roundings
 SG_ROUND_TRUNC, SG_ROUND_RINT = 0, 1
+# sg_multiscale_residual_max_levels(), restated like INTENSITY_HIST_MAX_BINS (a GPU test compares the two)
+SG_MSR_DEVICE_LEVELS = 4
 
 
 class ConvShape(C.Structure):
@@ -183,6 +185,11 @@ SIGNATURES = {
     'sg_sqdist_exact_workspace': (_sz, [_i32, _i32, _i64]),
     'sg_sqdist_exact': (C.c_int, [_p, _p, C.c_int, _i32, _i32, _i64, _p, _p, _sz, _p]),
     'sg_topk_merge': (C.c_int, [_p, _i32, _i32, _i64, _p, _i32, _p, _p, _p]),
+    'sg_multiscale_residual_max_levels': (_i32, []),
+    'sg_multiscale_residual_workspace': (_sz, [_i64, _i64, _i64, _i64, _i64, _i32]),
+    'sg_multiscale_residual': (C.c_int, [_p, C.c_int, _i32, _p, C.c_int, _i64, _p, _i64, _i64, _i64, _i64, _i64, _f, _f, _i32, _p,
+                                         C.POINTER(C.c_double), _p, _p, _p, _p, _sz, _p]),
+    'sg_latent_step': (C.c_int, [_p, _p, _p, _p, _p, _p, _p, _p, _i64, _i64, _f, _f, _f, _f, _i32, _i32, _p]),
     'sg_prof_enable': (C.c_int, [C.c_int]),
     'sg_prof_enabled': (C.c_int, []),
     'sg_prof_collect': (C.c_int, [C.POINTER(ProfEntry), _i32, C.POINTER(_i32)]),

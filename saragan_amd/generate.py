@@ -13,8 +13,9 @@ loader.  Takes generate_minimal's flags and:
   --inflight, --writers: the pipeline below.  --warn_clipped: the share of clipped voxels that draws a warning.
   --png, --preview_samples: the contact sheet of the shard's first samples.
 
-Sample i's latent row is np.random.default_rng([seed, i]).standard_normal(latent_dim, dtype=np.float32) and its label row is row i
-of the label table: a sample depends on the seed and its index only, not on the batch size, the shard or where a run resumed.
+Sample i's latent row is np.random.default_rng([seed, i]).standard_normal(latent_dim, dtype=np.float32) -- or, with
+--latents_path FILE.npy (float32 [N, latent_dim], e.g. the latents.npy of saragan_amd.project; --num_samples then defaults to N and
+the manifest records the path instead of the rule), row i of that table -- and its label row is row i of the label table: a sample depends on the seed and its index only, not on the batch size, the shard or where a run resumed.
 
 The pipeline: per batch G's forward pass, one store_volumes pass into a typed device buffer (with every sample's statistics), an
 asynchronous copy into one of --inflight pinned host buffers behind an event; while the next batch is generated the event is
@@ -35,7 +36,7 @@ from fractions import Fraction
 import numpy as np
 import torch
 
-from .generation import RestoredGenerator, add_model_arguments, add_preview_arguments, label_rows
+from .generation import RestoredGenerator, add_model_arguments, add_preview_arguments, label_rows, optional_num_samples
 
 OUT_DTYPES = ('uint16', 'int16', 'uint8', 'float32')
 LATENT_RULE = 'np.random.default_rng([seed, index]).standard_normal(latent_dim, dtype=np.float32)'
@@ -43,7 +44,10 @@ LATENT_RULE = 'np.random.default_rng([seed, index]).standard_normal(latent_dim, 
 
 def build_parser():
     p = add_model_arguments(argparse.ArgumentParser(prog='python -m saragan_amd.generate', description=__doc__.split('\n\n')[0]))
+    optional_num_samples(p)      # (required still, unless --latents_path says how many there are: plan())
     add_preview_arguments(p, 'preview_{R}of{W}.png')
+    p.add_argument('--latents_path', type=str, default=None,
+                   help='a float32 [N, latent_dim] .npy (project\'s latents.npy): row i is sample i\'s latent instead of the seeded rule')
     p.add_argument('--preview_samples', type=int, default=8, help='with --png: the sheet shows the first so many samples of this shard')
     p.add_argument('--out_dtype', default='uint16', choices=OUT_DTYPES)
     p.add_argument('--clip', type=str, default=None, help='LO,HI in data units (negative LO: --clip=LO,HI); default: the range of --out_dtype')
@@ -93,6 +97,18 @@ def plan(args, env=os.environ):
     """The checked settings of a run: shard, indices, names, scale / shift / clip.  ValueError on a bad flag; nothing is written."""
     if (args.data_mean is None) != (args.data_stddev is None):
         raise ValueError('give both --data_mean and --data_stddev, or neither')
+    latents = None
+    if getattr(args, 'latents_path', None):
+        latents = np.load(args.latents_path)
+        if latents.ndim != 2 or latents.shape[1] != args.latent_dim or latents.dtype != np.float32:
+            raise ValueError(f'--latents_path {args.latents_path}: expected float32 [N, latent_dim = {args.latent_dim}], got '
+                             f'{latents.dtype} {latents.shape}')
+        if args.num_samples is None:
+            args.num_samples = latents.shape[0]
+        if args.num_samples > latents.shape[0]:
+            raise ValueError(f'--num_samples {args.num_samples} exceeds the {latents.shape[0]} rows of --latents_path')
+    if args.num_samples is None:
+        raise ValueError('--num_samples is required (or --latents_path, whose rows are counted)')
     if args.num_samples < 0 or not 0 <= args.first_index or args.batch_size < 1:
         raise ValueError('--num_samples and --first_index are >= 0, --batch_size >= 1')
     if args.inflight < 1 or args.writers < 1 or args.preview_samples < 1:
@@ -114,7 +130,7 @@ def plan(args, env=os.environ):
     directory = os.path.join(args.output_dir or '.', f'generated_{args.phase}')
     indices = [i for i in range(args.first_index, args.num_samples) if i % w == r]
     names = {i: f'{args.name_prefix}{i:07d}.{args.format}' for i in indices}
-    return dict(rank=r, world=w, clip=clip, spacing=spacing, scale=scale, shift=shift, directory=directory, indices=indices, names=names,
+    return dict(rank=r, world=w, clip=clip, spacing=spacing, scale=scale, shift=shift, directory=directory, indices=indices, names=names, latents=latents,
                 manifest=os.path.join(directory, f'manifest_{r}of{w}.json'), sheet=os.path.join(directory, f'preview_{r}of{w}.png'))
 
 
@@ -231,7 +247,8 @@ def run(args, device=None, out=sys.stdout, env=os.environ):
                 finish(prev)
                 prev = None
             slot.drain(spent, records)
-            z = torch.from_numpy(latent_rows(args.seed, padded, args.latent_dim)).to(device, non_blocking=True)
+            rows = latent_rows(args.seed, padded, args.latent_dim) if p['latents'] is None else np.ascontiguousarray(p['latents'][padded])
+            z = torch.from_numpy(rows).to(device, non_blocking=True)
             cond = None if labels is None else torch.from_numpy(labels[padded]).to(device, non_blocking=True)
             ev = slot.events
             ev[0].record()
@@ -305,7 +322,8 @@ def _manifest(args, p, records, skipped, spent, wall, shape, integer):
     arguments = {k: v for k, v in vars(args).items()}
     return dict(arguments=arguments, definition=STORE_DEFINITION, scale=p['scale'], shift=p['shift'], clip=clip,
                 rounding=args.rounding, dtype=args.out_dtype, shape=[d, h, w] if c == 1 else [c, d, h, w], format=args.format,
-                shard=[p['rank'], p['world']], seed=args.seed, latent_dim=args.latent_dim, latent=LATENT_RULE,
+                shard=[p['rank'], p['world']], seed=args.seed, latent_dim=args.latent_dim,
+                latent=LATENT_RULE if p['latents'] is None else f'row index of {args.latents_path}',
                 files=records, skipped=[p['names'][i] for i in skipped], pooled=pooled,
                 seconds=dict(spent, wall=wall), volumes_per_second=len(records) / wall if wall > 0 else 0.0,
                 seconds_note='generation, store, download: device time between events, summed over batches; save: summed over the '

@@ -47,6 +47,14 @@ def add_model_arguments(p):
     return p
 
 
+def optional_num_samples(p):
+    """--num_samples stops being required: for the tools that can learn the count elsewhere (a latent table, a directory)."""
+    for a in p._actions:
+        if a.dest == 'num_samples':
+            a.required, a.default = False, None
+    return p
+
+
 def add_preview_arguments(p, what):
     p.add_argument('--png', default=False, action='store_true',
                    help=f'(new flag) also write {what}, a contact sheet of the samples (saragan_amd.preview)')
@@ -89,10 +97,11 @@ class RestoredGenerator:
         self.shape = get_current_input_shape(args.phase, args.batch_size, args.start_shape)
         self.base_shape = get_base_shape(args.start_shape)
 
-    def __call__(self, z, conditioning=None):
+    def __call__(self, z, conditioning=None, grad=False):
+        """grad=True records the pass for autograd (project.py differentiates it with respect to z)."""
         a = self.args
         kw = {} if conditioning is None else {'conditioning': conditioning}
-        with use_store(self.store), torch.no_grad():
+        with use_store(self.store), torch.set_grad_enabled(bool(grad)):
             return self.generator(z, 0.0, a.phase, self.base_shape, activation=a.activation, kernel_spec=a.kernel_spec,
                                   filter_spec=a.filter_spec, param=a.leakiness, size=a.network_size, is_reuse=False, **kw)
 

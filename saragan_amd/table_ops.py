@@ -2,8 +2,8 @@
 voxel-intensity histograms (metrics/intensity_metrics.py), rendered views (preview.py), the
 dataset pyramid of full-size volumes (prepare_data.py) and its resampler -- and the one write:
 typed volumes stored from the generator's output (generate.py).  Also the exact squared distances between typed
-integer rows and the running k nearest of the memorisation audit (metrics/memorisation.py).  Re-exported by
-functional."""
+integer rows and the running k nearest of the memorisation audit (metrics/memorisation.py), and the multi-scale
+residual loss of the projection with the update of its latents (project.py).  Re-exported by functional."""
 import math
 
 import torch
@@ -741,3 +741,278 @@ def nearest_rows(d, k, r_base=0, q_ids=None, best=None):
     with torch.cuda.device(d.device):
         check(lib.sg_topk_merge(_ptr(d), mq, mr, r_base, _ptr(q_ids), k, _ptr(best_d), _ptr(best_id), _stream()), 'sg_topk_merge')
     return best_d, best_id
+
+
+# ---- projection onto the generator: the multi-scale residual loss with its gradient, and the latents' update
+PROJECT_LEVELS_MAX = 6
+PROJECT_DEFINITION = (
+    't = (f32(x) - mean) / stddev, two roundings as gather_rows; r = f32(y) - t, one rounding; S_0 = f64(r), S_l(B) of a cube of edge '
+    '2^l = the sum of its eight children in the octree\'s order: the w pairs, then the h pairs, then the d pair; m_l = S_l * 8^-l; '
+    'Q_l = m_l^2 carried up the same tree to the edge-8 cubes that tile the volume from its origin (children outside count as +0), '
+    'the cubes added along w, those sums along h, those over (channel, d) in index order, each sum sequential from its first '
+    'element; terms_l = total / N_l with N_l = c d h w / 8^l; loss = f32(lambda_0 terms_0 + lambda_1 terms_1 + ...) in f64 and this '
+    'order; grad = k_0 r + (k_1 m_1 + (k_2 m_2 + ...)) in f64 from the coarsest level down, k_l = lambda_l * (2 / N_l) / 8^l, rounded '
+    'once to y\'s type (bf16 / f16 through an f32 rounded to odd)')
+LATENT_STEP_DEFINITION = (
+    'if loss < best_loss (never for NaN, not for an equal loss): best_loss = loss, z_best = z, best_step = step; then unless lr == 0, '
+    'in f32 and operation by operation: m = b1 m + (1 - b1) g; v = b2 v + ((1 - b2) g) g; z = z - (lr (m / c1)) / (sqrt(v / c2) + eps), '
+    'c_j = f32(1 - f64(b_j) ** step); then with sphere: z = f32(f64(z) * (sqrt(L) / sqrt(s))), s = the f64 sum of z_k^2 as 64 partial '
+    'sums over k = j, j + 64, ... in increasing k added pairwise 32, 16, ..., 1 apart (a row with s = 0, NaN or inf is left alone)')
+_LAMBDA_CACHE = {}
+
+
+def _msr_weights(weights, levels):
+    import numpy as np
+    lam = np.ones(levels, np.float32) if weights is None else np.asarray(
+        weights.detach().cpu().numpy() if torch.is_tensor(weights) else weights, dtype=np.float64)
+    if lam.shape != (levels,) or not np.all(np.isfinite(lam)) or np.any(lam < 0):
+        raise ValueError(f'multiscale_residual: weights are {levels} finite numbers >= 0, got {weights!r}')
+    return lam.astype(np.float32)
+
+
+def msr_coefficients(lam, shape, levels):
+    """k_l = lambda_l * (2 / N_l) / 8^l as Python floats (f64), N_l = c d h w / 8^l: the factors of the gradient."""
+    n0 = float(math.prod(shape))
+    return [float(lam[l]) * (2.0 / (n0 / 8.0 ** l)) / 8.0 ** l for l in range(levels)]
+
+
+def _round_once(g, dtype):
+    """The f64 array g rounded ONCE to dtype: float32 directly; bfloat16 / float16 through a float32 rounded to odd (the truncated
+    value with its last bit set when anything was cut off), after which the rounding to nearest even is the only one."""
+    import numpy as np
+    with np.errstate(over='ignore', invalid='ignore'):
+        f = g.astype(np.float32)
+        if dtype == torch.float32:
+            return torch.from_numpy(np.ascontiguousarray(f))
+        back = f.astype(np.float64)
+        rz = np.where(np.abs(back) > np.abs(g), np.nextafter(f, np.float32(0)), f).astype(np.float32)
+        bits = rz.view(np.uint32) | (back != g).astype(np.uint32)
+        odd = np.ascontiguousarray(bits).view(np.float32)
+        if dtype == torch.float16:
+            return torch.from_numpy(odd.astype(np.float16))
+    return torch.from_numpy(odd).to(torch.bfloat16)
+
+
+def _octree_up(a):
+    a = a[..., 0::2] + a[..., 1::2]
+    a = a[..., 0::2, :] + a[..., 1::2, :]
+    return a[..., 0::2, :, :] + a[..., 1::2, :, :]
+
+
+def _seq_sum_last(a):
+    acc = a[..., 0]
+    for k in range(1, a.shape[-1]):
+        acc = acc + a[..., k]
+    return acc
+
+
+def _msr_numpy(y, table, pos, mean, stddev, levels, lam):
+    """The CPU path: PROJECT_DEFINITION in numpy, operation by operation.  (loss f32 [n], terms f64 [n, levels], grad like y)."""
+    import numpy as np
+    yf = y.float().numpy().astype(np.float32, copy=False)      # by index, whatever the strides (every type converts exactly)
+    n, c, d, h, w = yf.shape
+    rows = table.shape[0]
+    ks = msr_coefficients(lam, (c, d, h, w), levels)
+    with np.errstate(over='ignore', invalid='ignore', divide='ignore'):
+        t = np.full(yf.shape, np.nan, np.float32)
+        valid = (pos >= 0) & (pos < rows)
+        if valid.any():
+            x = np.empty((int(valid.sum()), c, d, h, w), np.float32)
+            np.copyto(x, table.numpy()[pos[valid]], casting='unsafe')
+            np.subtract(x, np.float32(mean), out=x)
+            np.divide(x, np.float32(stddev), out=x)
+            t[valid] = x
+        r = yf - t
+        S, means, terms = r.astype(np.float64), [], np.empty((n, levels), np.float64)
+        for l in range(levels):
+            if l:
+                S = _octree_up(S)
+            m = S * 0.125 ** l
+            means.append(m)
+            q = m * m
+            # (levels 5 and 6, which only this path takes, carry to cubes of the coarsest level's edge instead of 8)
+            carry = max(3, levels - 1)
+            edge = 1 << (carry - l)      # cells of level l along the edge of a carry cube
+            pad = [(0, 0), (0, 0)] + [(0, -s % edge) for s in q.shape[2:]]
+            q = np.pad(q, pad)
+            for _ in range(carry - l):
+                q = _octree_up(q)
+            total = _seq_sum_last(_seq_sum_last(q))      # along w, then along h: [n, c, nd8]
+            total = _seq_sum_last(total.reshape(n, -1))
+            terms[:, l] = total / (float(c * d * h * w) / 8.0 ** l)
+        acc = np.float64(lam[0]) * terms[:, 0]
+        for l in range(1, levels):
+            acc = acc + np.float64(lam[l]) * terms[:, l]
+        loss = acc.astype(np.float32)
+        g = ks[levels - 1] * means[levels - 1]
+        for l in range(levels - 2, -1, -1):
+            g = ks[l] * means[l] + g.repeat(2, axis=2).repeat(2, axis=3).repeat(2, axis=4)
+        grad = _round_once(np.ascontiguousarray(g), y.dtype)
+    if not y.is_contiguous():
+        grad = grad.contiguous(memory_format=torch.channels_last_3d)
+    return torch.from_numpy(loss), torch.from_numpy(terms), grad
+
+
+def multiscale_residual_raw(y, table, idx, mean=0.0, stddev=1.0, levels=3, weights=None, out=None):
+    """(loss f32 [n], terms f64 [n, levels], grad): the multi-scale residual loss between y [n, c, d, h, w] (f32 / bf16 / f16;
+    contiguous or channels_last_3d) and the rows idx of table [rows, c, d, h, w] (u8 / i8 / i16 / u16 / f16 / f32, contiguous, in its
+    stored type), normalised as gather_rows does, and d loss[i] / d y[i] in y's type and memory format -- PROJECT_DEFINITION, exactly:
+    two calls give the same bits, and a CPU tensor takes the same definition in numpy and gives them too.  idx: int32 [n] on y's
+    device, or host positions (uploaded); repeats are allowed; a position outside the table gives a NaN loss, NaN terms and NaN
+    gradients for that sample.  levels: 1 .. 6 on the CPU, 1 .. 4 on the device (two launches: sg_multiscale_residual); every extent a
+    multiple of 2^(levels - 1).  weights: `levels` numbers >= 0 (host values; None: ones).  out: a buffer for grad, of y's shape,
+    type, strides and device.  No autograd: multiscale_residual has it."""
+    if not torch.is_tensor(y) or not torch.is_tensor(table):
+        raise TypeError('multiscale_residual: y and table are tensors')
+    if y.dtype not in STORE_SRC_DT:
+        raise TypeError(f'multiscale_residual: y is float32, bfloat16 or float16, got {y.dtype}')
+    if table.dtype not in SRC_DT:
+        raise TypeError(f'multiscale_residual: tables are uint8, int8, int16, uint16, float16 or float32, got {table.dtype}')
+    if y.dim() != 5 or y.shape[1] < 1 or min(y.shape[2:]) < 1:
+        raise ValueError(f'multiscale_residual: expected y [n, c, d, h, w] with no empty extent, got {tuple(y.shape)}')
+    channels_last = not y.is_contiguous()
+    if channels_last and not y.is_contiguous(memory_format=torch.channels_last_3d):
+        raise ValueError('multiscale_residual: expected a contiguous or channels_last_3d y')
+    if table.dim() != 5 or tuple(table.shape[1:]) != tuple(y.shape[1:]) or not table.is_contiguous():
+        raise ValueError(f'multiscale_residual: expected a contiguous table [rows, {", ".join(str(s) for s in y.shape[1:])}], got '
+                         f'{tuple(table.shape)}')
+    if table.device != y.device:
+        raise ValueError('multiscale_residual: y and table on different devices')
+    levels = int(levels)
+    if not 1 <= levels <= PROJECT_LEVELS_MAX:
+        raise ValueError(f'multiscale_residual: levels is 1 .. {PROJECT_LEVELS_MAX}, got {levels}')
+    for name, s in zip('dhw', y.shape[2:]):
+        if s % (1 << (levels - 1)):
+            raise ValueError(f'multiscale_residual: {name} = {s} is not a multiple of 2^{levels - 1} for {levels} levels')
+    if not (math.isfinite(float(mean)) and math.isfinite(float(stddev))) or float(stddev) == 0.0:
+        raise ValueError(f'multiscale_residual: mean and stddev are finite and stddev is not 0, got {mean!r} and {stddev!r}')
+    lam = _msr_weights(weights, levels)
+    if out is not None and (not torch.is_tensor(out) or out.shape != y.shape or out.dtype != y.dtype or out.device != y.device
+                            or out.stride() != y.stride()):
+        raise ValueError(f'multiscale_residual: out must be a {y.dtype} {tuple(y.shape)} tensor with y\'s strides on {y.device}')
+    n, c, d, h, w = y.shape
+    import numpy as np
+    if torch.is_tensor(idx) and idx.is_cuda:
+        if idx.device != y.device or idx.dtype != torch.int32 or tuple(idx.shape) != (n,) or not idx.is_contiguous():
+            raise ValueError(f'multiscale_residual: device positions are a contiguous int32 [{n}] tensor on y\'s device')
+    else:
+        pos = np.ascontiguousarray(idx.numpy() if torch.is_tensor(idx) else idx)
+        if pos.shape != (n,) or (pos.size and not np.issubdtype(pos.dtype, np.integer)):
+            raise ValueError(f'multiscale_residual: expected {n} integer positions, got {pos.dtype} {pos.shape}')
+        pos = pos.astype(np.int64)
+        if y.is_cuda:
+            idx = torch.from_numpy(np.clip(pos, -1, 2 ** 31 - 1).astype(np.int32)).to(y.device)
+    if not y.is_cuda:
+        loss, terms, grad = _msr_numpy(y, table, pos, mean, stddev, levels, lam)
+        return loss, terms, (grad if out is None else out.copy_(grad))
+    if levels > _lib.SG_MSR_DEVICE_LEVELS:
+        raise ValueError(f'multiscale_residual: the device kernel reduces cubes of edge 8 in registers: levels <= {_lib.SG_MSR_DEVICE_LEVELS} '
+                         f'on the device, got {levels} (the CPU path takes up to {PROJECT_LEVELS_MAX})')
+    import ctypes as C
+    lib = _lib.load()
+    key = (tuple(float(v) for v in lam), str(y.device))
+    lam_dev = _LAMBDA_CACHE.get(key)
+    if lam_dev is None:
+        lam_dev = _LAMBDA_CACHE[key] = torch.from_numpy(lam.copy()).to(y.device)
+    ks = (C.c_double * levels)(*msr_coefficients(lam, (c, d, h, w), levels))
+    grad = torch.empty_like(y) if out is None else out      # (empty_like preserves y's memory format)
+    terms = torch.empty((n, levels), device=y.device, dtype=torch.float64)
+    loss = torch.empty((n,), device=y.device, dtype=torch.float32)
+    with torch.cuda.device(y.device):
+        nbytes = lib.sg_multiscale_residual_workspace(n, c, d, h, w, levels)
+        ws = torch.empty(max(nbytes, 8) // 8, device=y.device, dtype=torch.float64)
+        check(lib.sg_multiscale_residual(_ptr(y), STORE_SRC_DT[y.dtype], 1 if channels_last else 0, _ptr(table), SRC_DT[table.dtype],
+                                         table.shape[0], _ptr(idx), n, c, d, h, w, float(mean), float(stddev), levels, _ptr(lam_dev), ks,
+                                         _ptr(grad), _ptr(terms), _ptr(loss), _ptr(ws), nbytes, _stream()), 'sg_multiscale_residual')
+    return loss, terms, grad
+
+
+class _MultiscaleResidual(torch.autograd.Function):
+    @staticmethod
+    def forward(ctx, y, table, idx, mean, stddev, levels, weights):
+        loss, terms, grad = multiscale_residual_raw(y.detach(), table, idx, mean, stddev, levels, weights)
+        ctx.save_for_backward(grad)
+        ctx.mark_non_differentiable(terms)
+        return loss, terms
+
+    @staticmethod
+    def backward(ctx, g_loss, _g_terms):
+        if not ctx.needs_input_grad[0]:
+            return (None,) * 7
+        grad, = ctx.saved_tensors
+        return (grad * g_loss.view(-1, 1, 1, 1, 1).to(grad.dtype),) + (None,) * 6
+
+
+def multiscale_residual(y, table, idx, mean=0.0, stddev=1.0, levels=3, weights=None):
+    """(loss f32 [n], terms f64 [n, levels]) of multiscale_residual_raw, with autograd: the gradient is computed in the same pass
+    and kept, so loss.sum().backward() delivers it to y (times the incoming gradient of every sample's loss; times 1 is exact)."""
+    return _MultiscaleResidual.apply(y, table, idx, mean, stddev, levels, weights)
+
+
+def _latent_step_numpy(z, m, v, g, loss, best_loss, z_best, best_step, lr, b1, b2, eps, step, sphere):
+    """The CPU path: LATENT_STEP_DEFINITION in numpy, operation by operation, in place."""
+    import numpy as np
+    f = np.float32
+    z, m, v, g, loss, best_loss, z_best, best_step = (t.numpy() for t in (z, m, v, g, loss, best_loss, z_best, best_step))
+    with np.errstate(over='ignore', invalid='ignore', divide='ignore'):
+        take = loss < best_loss
+        z_best[take] = z[take]
+        best_loss[take] = loss[take]
+        best_step[take] = step
+        if f(lr) == 0:
+            return
+        lr, b1, b2, eps = f(lr), f(b1), f(b2), f(eps)
+        omb1, omb2 = f(1) - b1, f(1) - b2
+        c1, c2 = f(1.0 - float(b1) ** step), f(1.0 - float(b2) ** step)
+        m[:] = b1 * m + omb1 * g
+        v[:] = b2 * v + (omb2 * g) * g
+        z[:] = z - (lr * (m / c1)) / (np.sqrt(v / c2) + eps)
+        if not sphere:
+            return
+        n, L = z.shape
+        z64 = z.astype(np.float64)
+        sq = np.pad(z64 * z64, [(0, 0), (0, -L % 64)]).reshape(n, -1, 64)
+        p = sq[:, 0]
+        for k in range(1, sq.shape[1]):
+            p = p + sq[:, k]
+        for s in (32, 16, 8, 4, 2, 1):
+            p = p[:, :s] + p[:, s:2 * s]
+        s = p[:, 0]
+        ok = (s > 0) & np.isfinite(s)
+        scale = np.sqrt(np.float64(L)) / np.sqrt(np.where(ok, s, 1.0))
+        z[ok] = (z64 * scale[:, None]).astype(np.float32)[ok]
+
+
+def latent_step_(z, m, v, grad_z, loss, best_loss, z_best, best_step, lr, step, beta1=0.9, beta2=0.999, eps=1e-8, sphere=False):
+    """One iteration of the projection on the latents z [n, L], in place on z, m, v, best_loss [n], z_best [n, L] and best_step (int32
+    [n]); grad_z [n, L] and loss [n] are this iteration's (all float32, contiguous, on one device) -- LATENT_STEP_DEFINITION:
+    first the best latent so far is kept (a NaN loss never wins, an equal loss does not replace), then Adam moves z, then with
+    sphere=True the row is rescaled to norm sqrt(L).  lr and step (>= 1) are host numbers: the caller knows the schedule, nothing is
+    read back.  lr = 0 only scores: z, m and v stay.  On the device one launch, one wave per row (sg_latent_step); CPU tensors take
+    the same definition in numpy and give the same bits.  Returns z."""
+    ts = (z, m, v, grad_z, loss, best_loss, z_best, best_step)
+    if not all(torch.is_tensor(t) for t in ts):
+        raise TypeError('latent_step_: expected tensors')
+    if z.dim() != 2 or z.shape[1] < 1:
+        raise ValueError(f'latent_step_: z is [n, L] with L >= 1, got {tuple(z.shape)}')
+    n, L = z.shape
+    for name, t, shape, dt in (('z', z, (n, L), torch.float32), ('m', m, (n, L), torch.float32), ('v', v, (n, L), torch.float32),
+                               ('grad_z', grad_z, (n, L), torch.float32), ('loss', loss, (n,), torch.float32),
+                               ('best_loss', best_loss, (n,), torch.float32), ('z_best', z_best, (n, L), torch.float32),
+                               ('best_step', best_step, (n,), torch.int32)):
+        if tuple(t.shape) != shape or t.dtype != dt or t.device != z.device or not t.is_contiguous() or t.requires_grad:
+            raise ValueError(f'latent_step_: {name} must be a contiguous {dt} {shape} tensor on {z.device} that does not require grad')
+    step = int(step)
+    if step < 1 or step >= 2 ** 31:
+        raise ValueError(f'latent_step_: step counts from 1, got {step}')
+    lr, beta1, beta2, eps = float(lr), float(beta1), float(beta2), float(eps)
+    if not (lr >= 0.0 and math.isfinite(lr)) or not 0.0 <= beta1 < 1.0 or not 0.0 <= beta2 < 1.0 or not (eps > 0.0 and math.isfinite(eps)):
+        raise ValueError(f'latent_step_: lr >= 0, betas in [0, 1) and eps > 0, got lr={lr!r}, betas=({beta1!r}, {beta2!r}), eps={eps!r}')
+    if not z.is_cuda:
+        _latent_step_numpy(z, m, v, grad_z, loss, best_loss, z_best, best_step, lr, beta1, beta2, eps, step, bool(sphere))
+        return z
+    lib = _lib.load()
+    with torch.cuda.device(z.device):
+        check(lib.sg_latent_step(_ptr(z), _ptr(m), _ptr(v), _ptr(grad_z), _ptr(loss), _ptr(best_loss), _ptr(z_best), _ptr(best_step), n, L,
+                                 lr, beta1, beta2, eps, step, 1 if sphere else 0, _stream()), 'sg_latent_step')
+    return z
