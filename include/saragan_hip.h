@@ -899,6 +899,28 @@ int sg_latent_step(float* z, float* m, float* v, const float* grad_z, const floa
                    int32_t* best_step, int64_t n, int64_t L, float lr, float beta1, float beta2, float eps, int32_t step,
                    int32_t sphere, sg_stream_t st);
 
+/* ---- shell-binned power spectra (csrc/spectrum.hip; table_ops.power_spectrum) --------------------------------------
+ * x [n, d, h, w] of the source type dt (any sg_src_dtype, SG_SRC_BF16 included), contiguous, on the device.  Per sample:
+ *   t = (double)x * scale + shift, two roundings in f64;  F = the half spectrum (kw = 0 .. w / 2) of t as three one-axis passes
+ *   (W, H, D) of f64 matrix products on v_mfma_f64_16x16x4_f64;  P = Fr^2 + Fi^2;  g = 1 at kw = 0 and kw = w / 2 (w even), else 2;
+ *   radial[i][c] = sum g P over the coefficients whose r2 = (f2_d[kd] + f2_h[kh]) + f2_w[kw] falls into column c: 0 where
+ *   r2 == 0, otherwise min(1 + #{b >= 1 : edges2[b] <= r2}, bins);
+ *   axes[i] = axis_d (d / 2 + 1 sums over min(kd, d - kd) = q), then axis_h (h / 2 + 1), then axis_w (w / 2 + 1 sums at kw = q).
+ * All DEVICE f64: mats = Cd^T [d][d], Sd^T [d][d], Ch^T [h][h], Sh^T [h][h], Cw^T [w][w / 2 + 1], Sw^T [w][w / 2 + 1], each
+ * stored as Mt[j][k] = trig[(k j) mod n] * window[j];  f2 = f2_d [d], f2_h [h], f2_w [w];  edges2 [bins + 1], non-decreasing;
+ * radial [n][bins + 1];  axes [n][(d / 2 + 1) + (h / 2 + 1) + (w / 2 + 1)];  workspace: sg_power_spectrum_workspace(n, d, h, w)
+ * bytes, 8-byte aligned, scratch (the planar complex intermediates and one partial row per block of the last pass).
+ * Every sum has a fixed order that depends on (d, h, w, bins) only: no floating-point atomics; two calls, another batch size or
+ * another position in the batch give the same bits per sample.  Extents need not be multiples of anything; 64-bit offsets.
+ * SG_EINVAL before any launch: an extent below 1 or above sg_power_spectrum_max_extent(), bins outside 1 .. 4096, an unknown dt,
+ * a scale or shift that is not finite, n < 0, a NULL pointer with work to do.  SG_EWORKSPACE: the workspace is too small.
+ * SG_EALIGN: x not aligned to its element size, another pointer not 8-byte aligned.  n == 0: SG_OK, nothing launched. */
+int32_t sg_power_spectrum_max_extent(void);      /* 1024 */
+size_t sg_power_spectrum_workspace(int64_t n, int64_t d, int64_t h, int64_t w);
+int sg_power_spectrum(const void* x, sg_src_dtype dt, int64_t n, int64_t d, int64_t h, int64_t w, double scale, double shift,
+                      const double* mats, const double* f2, const double* edges2, int32_t bins, double* radial, double* axes,
+                      void* workspace, size_t workspace_bytes, sg_stream_t st);
+
 /* ---- opt-in kernel timing (used by bench.py's roofline leg) ------------------------------------- */
 /* When enabled, every sg_conv3d_fwd / sg_conv3d_wgrad launch is bracketed by hipEvents on its stream.
  * sg_prof_collect synchronises those events and returns, per kind (0 = conv fwd, 1 = wgrad) and per

@@ -32,6 +32,9 @@ SG_RESAMPLE_MAX_TAPS = 32
 SG_ROUND_TRUNC, SG_ROUND_RINT = 0, 1
 # sg_multiscale_residual_max_levels(), restated like INTENSITY_HIST_MAX_BINS (a GPU test compares the two)
 SG_MSR_DEVICE_LEVELS = 4
+# sg_power_spectrum_max_extent() and the most radial bins, restated like INTENSITY_HIST_MAX_BINS (a GPU test compares the first)
+POWER_SPECTRUM_MAX_EXTENT = 1024
+POWER_SPECTRUM_MAX_BINS = 4096
 
 
 class ConvShape(C.Structure):
@@ -190,6 +193,10 @@ SIGNATURES = {
     'sg_multiscale_residual': (C.c_int, [_p, C.c_int, _i32, _p, C.c_int, _i64, _p, _i64, _i64, _i64, _i64, _i64, _f, _f, _i32, _p,
                                          C.POINTER(C.c_double), _p, _p, _p, _p, _sz, _p]),
     'sg_latent_step': (C.c_int, [_p, _p, _p, _p, _p, _p, _p, _p, _i64, _i64, _f, _f, _f, _f, _i32, _i32, _p]),
+    'sg_power_spectrum_max_extent': (_i32, []),
+    'sg_power_spectrum_workspace': (_sz, [_i64, _i64, _i64, _i64]),
+    'sg_power_spectrum': (C.c_int, [_p, C.c_int, _i64, _i64, _i64, _i64, C.c_double, C.c_double, _p, _p, _p, _i32, _p, _p, _p, _sz,
+                                    _p]),
     'sg_prof_enable': (C.c_int, [C.c_int]),
     'sg_prof_enabled': (C.c_int, []),
     'sg_prof_collect': (C.c_int, [C.POINTER(ProfEntry), _i32, C.POINTER(_i32)]),

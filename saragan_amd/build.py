@@ -8,7 +8,7 @@ import sys
 HERE = os.path.dirname(os.path.abspath(__file__))
 CSRC = os.path.join(HERE, 'csrc')
 LIB = os.path.join(HERE, 'libsaragan_hip.so')
-SOURCES = ['conv3d.hip', 'conv3p.hip', 'conv3w.hip', 'wgrad.hip', 'elementwise.hip', 'optim.hip', 'lamb.hip', 'spectral.hip', 'prof.hip', 'small.hip', 'subpix.hip', 'gemm.hip', 'metrics.hip', 'augment.hip', 'augment_affine.hip', 'mbstd.hip', 'cond.hip', 'pdist.hip', 'deck.hip', 'hist.hip', 'render.hip', 'pyramid.hip', 'resample.hip', 'export.hip', 'sqdist_exact.hip', 'project.hip']
+SOURCES = ['conv3d.hip', 'conv3p.hip', 'conv3w.hip', 'wgrad.hip', 'elementwise.hip', 'optim.hip', 'lamb.hip', 'spectral.hip', 'prof.hip', 'small.hip', 'subpix.hip', 'gemm.hip', 'metrics.hip', 'augment.hip', 'augment_affine.hip', 'mbstd.hip', 'cond.hip', 'pdist.hip', 'deck.hip', 'hist.hip', 'render.hip', 'pyramid.hip', 'resample.hip', 'export.hip', 'sqdist_exact.hip', 'project.hip', 'spectrum.hip']
 HEADERS = ['common.h', 'prof.h', 'conv_args.h', os.path.join('..', '..', 'include', 'saragan_hip.h')]
 FLAGS = ['--offload-arch=gfx950', '-O3', '-std=c++17', '-fPIC', '-Wall', '-Wno-unused-function']
 # The MFMA kernels' off-phases share their SIMD with the other wave group's MFMAs, and packed-f32 VALU ops
@@ -35,7 +35,9 @@ FILE_FLAGS = {'conv3d.hip': ['-fno-slp-vectorize', '-save-temps=obj'], 'wgrad.hi
               # the export's map back to data units (x * scale + shift) rounds twice, as its numpy twin does
               'export.hip': ['-ffp-contract=off'],
               # the projection loss and the latents' update round operation by operation, as their numpy twins do
-              'project.hip': ['-ffp-contract=off']}
+              'project.hip': ['-ffp-contract=off'],
+              # the spectrum's map x * scale + shift, its squares and the sum of three squared frequencies round one by one
+              'spectrum.hip': ['-ffp-contract=off']}
 
 
 def _hipcc():

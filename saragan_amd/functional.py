@@ -1328,4 +1328,5 @@ from .table_ops import block_pyramid, pyramid_offsets, resample_taps, resample_v
 from .table_ops import STORE_DEFINITION, store_volumes  # noqa: E402,F401
 from .table_ops import nearest_rows, sqdist_exact  # noqa: E402,F401
 from .table_ops import LATENT_STEP_DEFINITION, PROJECT_DEFINITION, latent_step_, multiscale_residual, multiscale_residual_raw  # noqa: E402,F401
+from .table_ops import SpectrumPlan, power_spectrum  # noqa: E402,F401
 

@@ -180,6 +180,16 @@ def build_parser():
                         '--hist_range=LO,HI')
     p.add_argument('--hist_levels', type=int, default=1,
                    help='with --compute_intensity_hist: 1 = the volumes; N = plus N - 1 detail levels of the Laplacian pyramid')
+    # (new flags) power-spectrum distances, a direct 3-D DFT on f64 MFMAs: metrics/spectrum_metrics.py
+    p.add_argument('--compute_power_spectrum', default=False, action='store_true',
+                   help='log-spectral distance (radial and per axis) and high-frequency excess between the shell-binned power '
+                        'spectra of reals and fakes, in dB')
+    p.add_argument('--spectrum_spacing', type=str, default='1,1,1',
+                   help='with --compute_power_spectrum: voxel spacing d,h,w in mm (frequencies are in cycles / mm)')
+    p.add_argument('--spectrum_bins', type=int, default=None,
+                   help='with --compute_power_spectrum: radial columns next to DC (default: the largest extent // 2)')
+    p.add_argument('--spectrum_window', type=str, default='none', choices=['none', 'hann'],
+                   help='with --compute_power_spectrum: hann tapers every axis (the mean is not removed: DC leaks into |k| <= 1)')
     # (not in the reference) sample previews: PNG contact sheets of fixed latents under <logdir>/previews (preview.py)
     p.add_argument('--preview_every_nsteps', type=int, default=0,
                    help='(not in the reference) write a sheet of the fixed latents every N images (0: off)')
@@ -293,6 +303,35 @@ def finalize_hist_args(args):
     return args
 
 
+def finalize_spectrum_args(args):
+    """--compute_power_spectrum: --spectrum_spacing 'd,h,w' becomes a tuple of three positive floats; refused at start-up
+    where the run could not use it."""
+    if not getattr(args, 'compute_power_spectrum', False):
+        return args
+    from ._lib import POWER_SPECTRUM_MAX_BINS, POWER_SPECTRUM_MAX_EXTENT
+    text = getattr(args, 'spectrum_spacing', '1,1,1')
+    if not isinstance(text, tuple):
+        try:
+            sp = tuple(float(v) for v in str(text).split(','))
+        except ValueError:
+            sp = ()
+        if len(sp) != 3 or not all(v > 0 and v < float('inf') for v in sp):
+            raise SystemExit(f'--spectrum_spacing: expected three positive numbers d,h,w (mm), got {text!r}')
+        args.spectrum_spacing = sp
+    bins = getattr(args, 'spectrum_bins', None)
+    if bins is not None and not 1 <= bins <= POWER_SPECTRUM_MAX_BINS:
+        raise SystemExit(f'--spectrum_bins must lie in [1, {POWER_SPECTRUM_MAX_BINS}], got {bins}')
+    if getattr(args, 'spectrum_window', 'none') not in ('none', 'hann'):
+        raise SystemExit(f'--spectrum_window is none or hann, got {args.spectrum_window!r}')
+    shape = parse_tuple(args.final_shape) if getattr(args, 'final_shape', None) else ()
+    if shape and shape[0] != 1:
+        raise SystemExit(f'--compute_power_spectrum reads one channel, --final_shape has {shape[0]}')
+    if shape and max(shape[1:]) > POWER_SPECTRUM_MAX_EXTENT:
+        raise SystemExit(f'--compute_power_spectrum: extents above {POWER_SPECTRUM_MAX_EXTENT} are not supported, --final_shape '
+                         f'is {args.final_shape}')
+    return args
+
+
 def finalize_preview_args(args):
     """--preview_*: the views and the window are parsed (args.preview_views: [(mode, axis, index)], args.preview_window: (lo,
     hi) in data units); refused at start-up where the run could not use them."""
@@ -335,6 +374,7 @@ def finalize_args(args):
     finalize_augment_args(args)
     finalize_mbstd_args(args)
     finalize_hist_args(args)
+    finalize_spectrum_args(args)
     finalize_preview_args(args)
     if getattr(args, 'conditioning_path', None) and args.architecture != 'pgan':
         raise SystemExit(f'--conditioning_path is offered for the pgan architecture only, got {args.architecture!r}')

@@ -9,7 +9,8 @@ the Inception graph the reference downloads (metrics/fid_new.py:291-318): --comp
 every evaluation and no 'FID' key.  In its place (not in the reference): --compute_mmd, --compute_nn_accuracy and
 --compute_precision_recall, three download-free two-sample statistics over the POOLED evaluated batches
 (metrics/sample_metrics.py), and --compute_intensity_hist, the distances of the voxel-intensity histograms in data units
-(metrics/intensity_metrics.py; the reference's metrics/kms.py, which its loop never calls)."""
+(metrics/intensity_metrics.py; the reference's metrics/kms.py, which its loop never calls), and --compute_power_spectrum, the
+log-spectral distances and the high-frequency excess of the shell-binned power spectra (metrics/spectrum_metrics.py)."""
 import time
 
 import numpy as np
@@ -29,7 +30,7 @@ def get_compute_metrics_dict(args):
     """utils.py:267-277."""
     return {k: bool(getattr(args, k, False)) for k in
             ('compute_FID', 'compute_swds', 'compute_ssims', 'compute_psnrs', 'compute_mses', 'compute_nrmses') + SAMPLE_FLAGS
-            + ('compute_intensity_hist',)}
+            + ('compute_intensity_hist', 'compute_power_spectrum')}
 
 
 def _gather_to_rank0(fake, global_size):
@@ -44,7 +45,8 @@ def _gather_to_rank0(fake, global_size):
 
 def save_metrics(writer, sess, npy_data, gen_sample, batch_size, global_size, global_step, imagesize_xy, horovod,
                  hyperparam_opt_inter_trial, compute_metrics, num_metric_samples, data_mean, data_stddev, verbose, suffix='',
-                 keep=None, conditioning=None, pr_k=3, keep_sets=None, hist_range=None, hist_levels=1, keep_hists=None):
+                 keep=None, conditioning=None, pr_k=3, keep_sets=None, hist_range=None, hist_levels=1, keep_hists=None,
+                 spectrum=None, keep_spectra=None):
     """Same arguments and return value as the reference (a dict with the keys swd, ssim, psnr, mse, nrmse of the enabled
     metrics).  `keep`: a list that receives (real_batch, fake_batch) of every evaluated batch (tests).  `conditioning` (not in
     the reference): the step graph's label placeholder -- the fakes are generated with the label rows of the real batch they
@@ -57,7 +59,11 @@ def save_metrics(writer, sess, npy_data, gen_sample, batch_size, global_size, gl
     `hist_range` = (lo, hi) in data units -- the batches are normalised, so the kernel maps them back with scale = data_stddev,
     shift = data_mean (1, 0 for data that is not normalised) -- on `hist_levels` levels; nothing is retained, the distances are
     read off the counts after the loop (keys intensity_ks, intensity_w1, intensity_gap: a list per level).  `keep_hists`: a
-    list that receives the accumulator's level count and, per batch, the two Laplacian pyramids (tests)."""
+    list that receives the accumulator's level count and, per batch, the two Laplacian pyramids (tests).
+    compute_power_spectrum (metrics/spectrum_metrics.py): every evaluated batch goes through a SpectrumAccumulator with the
+    options `spectrum` = {'spacing': (d, h, w) in mm, 'bins': B or None, 'window': 'none' | 'hann'} (all optional) and the same
+    map back to data units; only the two sum vectors are retained (keys spectrum_lsd, spectrum_lsd_d|h|w, spectrum_hf_excess,
+    spectrum_skipped_columns).  `keep_spectra`: a list that receives the accumulator after the loop (tests)."""
     def log(s):
         if verbose:
             print(s)
@@ -87,6 +93,9 @@ def save_metrics(writer, sess, npy_data, gen_sample, batch_size, global_size, gl
         normalised = data_mean is not None and data_stddev is not None
         hist = IM.IntensityAccumulator(hist_range[0], hist_range[1], data_stddev if normalised else 1.0,
                                        data_mean if normalised else 0.0, hist_levels)
+    spec, spec_wanted = None, bool(compute_metrics.get('compute_power_spectrum')) and rank0
+    if spec_wanted:
+        from . import spectrum_metrics as SPM      # (only a run that asks for it imports it)
     counter = 0
     while True:
         real_batch = npy_data.batch_mpi(batch_size) if horovod else npy_data.batch(batch_size)      # :94-97
@@ -131,6 +140,16 @@ def save_metrics(writer, sess, npy_data, gen_sample, batch_size, global_size, gl
                 fakes_kept.append(fake.reshape(fake.shape[0], -1).to(torch.float32))
             if hist is not None:
                 hist.add(real, fake, keep=keep_hists)
+            if spec_wanted:
+                if spec is None:      # (the first batch gives the shape: [n, 1, d, h, w])
+                    if real.dim() != 5 or real.shape[1] != 1:
+                        raise ValueError(f'compute_power_spectrum reads [n, 1, d, h, w] volumes, got {tuple(real.shape)}')
+                    normalised = data_mean is not None and data_stddev is not None
+                    opts = dict(spectrum or {})
+                    spec = SPM.SpectrumAccumulator(tuple(real.shape[2:]), opts.get('spacing', (1.0, 1.0, 1.0)), opts.get('bins'),
+                                                   opts.get('window', 'none'), data_stddev if normalised else 1.0,
+                                                   data_mean if normalised else 0.0)
+                spec.add(real, fake)
             for flag, fn, dest, name in (('compute_swds', SWD.get_swd_for_volumes, swds_local, 'swds'),
                                          ('compute_psnrs', SK.get_psnr, psnrs_local, 'psnrs'),
                                          ('compute_ssims', SK.get_ssim, ssims_local, 'ssims'),
@@ -166,6 +185,13 @@ def save_metrics(writer, sess, npy_data, gen_sample, batch_size, global_size, gl
             if keep_hists is not None:
                 keep_hists.append(hist.levels)
             for line in IM.format_lines(m):
+                log(line)
+            metrics.update(m)
+        if spec is not None:
+            m = spec.result()
+            if keep_spectra is not None:
+                keep_spectra.append(spec)
+            for line in SPM.format_lines(m):
                 log(line)
             metrics.update(m)
     return metrics

@@ -3,7 +3,8 @@ voxel-intensity histograms (metrics/intensity_metrics.py), render
 dataset pyramid of full-size volumes (prepare_data.py) and its resampler -- and the one write:
 typed volumes stored from the generator's output (generate.py).  Also the exact squared distances between typed
 integer rows and the running k nearest of the memorisation audit (metrics/memorisation.py), and the multi-scale
-residual loss of the projection with the update of its latents (project.py).  Re-exported by functional."""
+residual loss of the projection with the update of its latents (project.py), and the shell-binned power
+spectrum of typed volumes (metrics/spectrum_metrics.py).  Re-exported by functional."""
 import math
 
 import torch
@@ -1016,3 +1017,198 @@ def latent_step_(z, m, v, grad_z, loss, best_loss, z_best, best_step, lr, step, 
         check(lib.sg_latent_step(_ptr(z), _ptr(m), _ptr(v), _ptr(grad_z), _ptr(loss), _ptr(best_loss), _ptr(z_best), _ptr(best_step), n, L,
                                  lr, beta1, beta2, eps, step, 1 if sphere else 0, _stream()), 'sg_latent_step')
     return z
+
+
+# ---- shell-binned power spectra (metrics/spectrum_metrics.py)
+SPECTRUM_WINDOWS = ('none', 'hann')
+
+
+def trig_tables(n):
+    """(c, s): cos and sin of 2 pi m / n for m = 0 .. n - 1 in f64.  The angle is reduced to the first octant with integer
+    arithmetic on 8 m / n, so multiples of n / 4 give exactly 0 and +-1, odd multiples of n / 8 one shared sqrt(1/2), and mirrored
+    entries are bit-equal: c[n - m] == c[m], s[n - m] == -s[m], c[m + n / 2] == -c[m]."""
+    import numpy as np
+    n = int(n)
+    m = np.arange(n, dtype=np.int64)
+    quad = (4 * m) // n                          # the quadrant, 0 .. 3
+    p = 8 * m - 2 * quad * n                     # the angle inside the quadrant, in units of pi / (4 n): 0 <= p < 2 n
+    low = p <= n
+    a = np.where(low, p, 2 * n - p).astype(np.float64) * (np.pi / (4.0 * n))      # in [0, pi / 4]
+    ca, sa = np.cos(a), np.sin(a)
+    half = p == n
+    ca[half] = sa[half] = np.sqrt(0.5)
+    cq, sq = np.where(low, ca, sa), np.where(low, sa, ca)
+    c = np.choose(quad, [cq, -sq, -cq, sq]) + 0.0      # (+ 0.0: no negative zeros)
+    s = np.choose(quad, [sq, cq, -sq, -cq]) + 0.0
+    return c, s
+
+
+def spectrum_window(n, window):
+    """The window of one axis: ones, or the periodic Hann window 0.5 - 0.5 cos(2 pi j / n) from the same table.  An axis of
+    extent 1 is never windowed (its periodic Hann window would be the single value 0)."""
+    import numpy as np
+    if window == 'none' or int(n) == 1:
+        return np.ones(int(n), dtype=np.float64)
+    return 0.5 - 0.5 * trig_tables(n)[0]
+
+
+def spectrum_matrices(n, window='none', half=False):
+    """(Ct, St) of one axis, transposed for the kernel: Mt[j][k] = trig[(k j) mod n] * win[j], k = 0 .. n - 1 (half: 0 .. n // 2)."""
+    import numpy as np
+    n = int(n)
+    c, s = trig_tables(n)
+    win = spectrum_window(n, window)
+    k = np.arange(n // 2 + 1 if half else n, dtype=np.int64)
+    idx = (np.arange(n, dtype=np.int64)[:, None] * k[None, :]) % n
+    return np.ascontiguousarray(c[idx] * win[:, None]), np.ascontiguousarray(s[idx] * win[:, None])
+
+
+class SpectrumPlan:
+    """The host tables of power_spectrum for one volume shape (d, h, w) -- or (h, w), read as d = 1 --, voxel spacing in mm, number
+    of radial bins (default max(d, h, w) // 2) and window ('none' or 'hann'; with 'hann' the mean is NOT removed: Hann's transform
+    has three taps, so DC leaks into |k| <= 1 per axis, equally for both sets of a comparison).  Holds the six transposed matrices,
+    the squared frequencies f2 per axis, the squared column edges, the weighted coefficient counts of every column and profile
+    bin, and the device copies of the tables, made on first use per device."""
+
+    def __init__(self, shape, spacing=(1.0, 1.0, 1.0), bins=None, window='none'):
+        import numpy as np
+        shape = tuple(int(v) for v in shape)
+        if len(shape) == 2:
+            shape = (1,) + shape
+        if len(shape) != 3:
+            raise ValueError(f'SpectrumPlan: expected a shape (d, h, w) or (h, w), got {shape}')
+        if min(shape) < 1 or max(shape) > _lib.POWER_SPECTRUM_MAX_EXTENT:
+            raise ValueError(f'SpectrumPlan: extents lie in 1 .. {_lib.POWER_SPECTRUM_MAX_EXTENT}, got {shape}')
+        spacing = tuple(float(v) for v in spacing)
+        if len(spacing) == 2:
+            spacing = (1.0,) + spacing
+        if len(spacing) != 3 or not all(math.isfinite(v) and v > 0 for v in spacing):
+            raise ValueError(f'SpectrumPlan: the spacing is three positive numbers (mm), got {spacing}')
+        if bins is None:
+            bins = max(max(shape) // 2, 1)      # (a single voxel still has one column next to DC)
+        bins = int(bins)
+        if not 1 <= bins <= _lib.POWER_SPECTRUM_MAX_BINS:
+            raise ValueError(f'SpectrumPlan: bins lie in 1 .. {_lib.POWER_SPECTRUM_MAX_BINS}, got {bins}')
+        if window not in SPECTRUM_WINDOWS:
+            raise ValueError(f'SpectrumPlan: the window is one of {SPECTRUM_WINDOWS}, got {window!r}')
+        self.shape, self.spacing, self.bins, self.window = shape, spacing, bins, window
+        d, h, w = shape
+        self.wf = w // 2 + 1
+        self.mats = [m for n_, half in ((d, False), (h, False), (w, True)) for m in spectrum_matrices(n_, window, half)]
+        self.f2 = [(np.minimum(np.arange(n_), n_ - np.arange(n_)).astype(np.float64) / (n_ * sp)) ** 2
+                   for n_, sp in zip(shape, spacing)]
+        self.top = float((self.f2[0].max() + self.f2[1].max()) + self.f2[2].max())
+        self.edges2 = (np.arange(bins + 1, dtype=np.float64) * np.sqrt(self.top) / bins) ** 2
+        self.edges2[bins] = self.top
+        self.g = np.full(self.wf, 2.0)
+        self.g[0] = 1.0
+        if w % 2 == 0:
+            self.g[w // 2] = 1.0
+        self.q = [np.minimum(np.arange(n_), n_ - np.arange(n_)) for n_ in (d, h)] + [np.arange(self.wf)]
+        self.axis_len = (d // 2 + 1, h // 2 + 1, self.wf)
+        self.counts = np.zeros(bins + 1, dtype=np.float64)
+        for kd in range(d):      # plane by plane: the whole column map is only built where the twin asks for it
+            np.add.at(self.counts, self.columns(kd).ravel(), np.broadcast_to(self.g, (h, self.wf)).ravel())
+        self.axis_counts = (np.bincount(self.q[0], minlength=d // 2 + 1) * float(h * w),
+                            np.bincount(self.q[1], minlength=h // 2 + 1) * float(d * w), self.g * float(d * h))
+        self._columns = None
+        self._device = {}
+
+    def columns(self, kd=None):
+        """The radial column of every coefficient, int64 [d, h, wf] (kd given: of that plane, [h, wf]):
+        r2 = (f2_d[kd] + f2_h[kh]) + f2_w[kw]; column 0 where r2 == 0, else min(1 + #{b >= 1: edges2[b] <= r2}, bins)."""
+        import numpy as np
+        if kd is None:
+            if self._columns is None:
+                self._columns = np.stack([self.columns(k) for k in range(self.shape[0])])
+            return self._columns
+        r2 = (self.f2[0][kd] + self.f2[1][:, None]) + self.f2[2][None, :self.wf]
+        col = np.minimum(1 + np.searchsorted(self.edges2[1:], r2, 'right'), self.bins)
+        return np.where(r2 == 0, 0, col).astype(np.int64)
+
+    def centres(self):
+        """The frequency (cycles / mm) at the centre of every radial column; column 0 is DC."""
+        import numpy as np
+        e = np.sqrt(self.edges2)
+        return np.concatenate([[0.0], 0.5 * (e[:-1] + e[1:])])[:self.bins + 1]
+
+    def axis_frequencies(self):
+        import numpy as np
+        return tuple(np.arange(m) / (n_ * sp) for m, n_, sp in zip(self.axis_len, self.shape, self.spacing))
+
+    def device_tables(self, device):
+        import numpy as np
+        key = str(device)
+        if key not in self._device:
+            up = lambda a: torch.from_numpy(np.ascontiguousarray(a)).to(device)
+            self._device[key] = (up(np.concatenate([m.ravel() for m in self.mats])), up(np.concatenate(self.f2)), up(self.edges2))
+        return self._device[key]
+
+
+def _spectrum_numpy(x, plan, scale, shift):
+    """The numpy twin: the same map, window, columns and weights; np.fft.rfftn in f64, np.add.at into the columns."""
+    import numpy as np
+    d, h, w = plan.shape
+    n = x.shape[0]
+    radial = np.zeros((n, plan.bins + 1), dtype=np.float64)
+    axes = [np.zeros((n, m), dtype=np.float64) for m in plan.axis_len]
+    col = plan.columns().ravel()
+    win = [spectrum_window(n_, plan.window) for n_ in plan.shape]
+    for i in range(n):
+        t = x[i].astype(np.float64) * np.float64(scale) + np.float64(shift)
+        if plan.window != 'none':
+            t = t * win[0][:, None, None] * win[1][None, :, None] * win[2][None, None, :]
+        f = np.fft.rfftn(t, axes=(0, 1, 2))
+        p = (f.real ** 2 + f.imag ** 2) * plan.g[None, None, :]
+        np.add.at(radial[i], col, p.ravel())
+        np.add.at(axes[0][i], plan.q[0], p.sum(axis=(1, 2)))
+        np.add.at(axes[1][i], plan.q[1], p.sum(axis=(0, 2)))
+        axes[2][i] += p.sum(axis=(0, 1))
+    return radial, axes
+
+
+def power_spectrum(x, plan, scale=1.0, shift=0.0, workspace_mib=512):
+    """(radial f64 [n, bins + 1], (axis_d [n, d // 2 + 1], axis_h [n, h // 2 + 1], axis_w [n, w // 2 + 1])): the shell-binned power
+    spectrum of every volume of x after t = f64(x) * scale + shift (two roundings), as DESIGN.md 4.14 defines it: sums of g |F|^2
+    over the half spectrum, per radial column of the plan and per |k| along each axis.  x: [n, d, h, w] or [n, 1, d, h, w] (one
+    channel), or [n, h, w] for a plan with d = 1; u8 / i8 / i16 / u16 / f16 / bf16 / f32.  On the device: sg_power_spectrum, three
+    passes of f64 MFMAs per chunk of samples, chunked so that the workspace stays under workspace_mib -- a sample's bits depend on
+    neither the chunking nor the batch.  A CPU tensor takes the numpy twin (np.fft.rfftn)."""
+    if not isinstance(plan, SpectrumPlan):
+        raise TypeError(f'power_spectrum: expected a SpectrumPlan, got {type(plan).__name__}')
+    if torch.is_tensor(x) and x.dim() == 3:
+        x = x.unsqueeze(1)
+    x, (n, d, h, w, c) = view_volumes(x)
+    if c != 1:
+        raise ValueError(f'power_spectrum: one channel, got {c}')
+    if (d, h, w) != plan.shape:
+        raise ValueError(f'power_spectrum: the plan is for volumes of {plan.shape}, got {(d, h, w)}')
+    scale, shift = float(scale), float(shift)
+    if not (math.isfinite(scale) and math.isfinite(shift)):
+        raise ValueError(f'power_spectrum: scale {scale} and shift {shift} must be finite')
+    if not workspace_mib > 0:
+        raise ValueError(f'power_spectrum: workspace_mib {workspace_mib} must be positive')
+    nrad, alen = plan.bins + 1, sum(plan.axis_len)
+    cut = (plan.axis_len[0], plan.axis_len[0] + plan.axis_len[1])
+    if not x.is_cuda:
+        xn = x.reshape(n, d, h, w)
+        xn = xn.float().numpy() if xn.dtype == torch.bfloat16 else xn.numpy()
+        radial, axes = _spectrum_numpy(xn, plan, scale, shift)
+        return torch.from_numpy(radial), tuple(torch.from_numpy(a) for a in axes)
+    radial = torch.empty((n, nrad), device=x.device, dtype=torch.float64)
+    axes = torch.empty((n, alen), device=x.device, dtype=torch.float64)
+    if n:
+        lib = _lib.load()
+        mats, f2, edges2 = plan.device_tables(x.device)
+        per = int(lib.sg_power_spectrum_workspace(1, d, h, w))
+        chunk = max(1, min(n, int(workspace_mib * 2 ** 20) // per))
+        nbytes = int(lib.sg_power_spectrum_workspace(chunk, d, h, w))
+        ws = torch.empty(nbytes, device=x.device, dtype=torch.uint8)
+        flat = x.reshape(n, d * h * w)
+        with torch.cuda.device(x.device):
+            for i in range(0, n, chunk):
+                m = min(chunk, n - i)
+                check(lib.sg_power_spectrum(_ptr(flat[i:i + m]), HIST_DT[x.dtype], m, d, h, w, scale, shift, _ptr(mats), _ptr(f2),
+                                            _ptr(edges2), plan.bins, _ptr(radial[i:i + m]), _ptr(axes[i:i + m]), _ptr(ws), nbytes,
+                                            _stream()), 'sg_power_spectrum')
+    return radial, (axes[:, :cut[0]], axes[:, cut[0]:cut[1]], axes[:, cut[1]:])

@@ -168,22 +168,34 @@ def _run_training(args, device, max_steps_per_phase, log_every):
 
         metric_sets = getattr(args, '_metric_sets', None)    # tests: receives (phase, tag, n, distance matrix) per pooled evaluation
         metric_hists = getattr(args, '_metric_hists', None)  # tests: receives (phase, tag, pyramids of the batches..., levels)
+        metric_spectra = getattr(args, '_metric_spectra', None)  # tests: receives (phase, tag, the evaluation's accumulator)
+        spectrum_opts = None
+        if metric_flags.get('compute_power_spectrum'):
+            spacing = getattr(args, 'spectrum_spacing', (1.0, 1.0, 1.0))
+            if isinstance(spacing, str):      # (a namespace that did not go through main.finalize_args)
+                spacing = tuple(float(v) for v in spacing.split(','))
+            spectrum_opts = {'spacing': spacing, 'bins': getattr(args, 'spectrum_bins', None),
+                             'window': getattr(args, 'spectrum_window', 'none')}
 
         def run_metrics(subset, nsamples, suffix='', tag='loop'):
             kept = [] if metric_tap is not None else None
             sets = [] if metric_sets is not None else None
             hists = [] if metric_hists is not None else None
+            spectra = [] if metric_spectra is not None else None
             m = save_metrics(None, sess, subset, gen_sample, getattr(args, 'metrics_batch_size', 16), global_size, global_step,
                              get_xy_dim(phase, args.start_shape), horovod, False, metric_flags, nsamples, args.data_mean,
                              args.data_stddev, verbose, suffix=suffix, keep=kept, conditioning=conditioning,
                              pr_k=getattr(args, 'pr_k', 3), keep_sets=sets, hist_range=getattr(args, 'hist_range', None),
-                             hist_levels=getattr(args, 'hist_levels', 1), keep_hists=hists)
+                             hist_levels=getattr(args, 'hist_levels', 1), keep_hists=hists, spectrum=spectrum_opts,
+                             keep_spectra=spectra)
             if metric_tap is not None:
                 metric_tap.append((phase, tag + suffix, m, kept))
             if metric_sets is not None:
                 metric_sets.extend((phase, tag + suffix, n, D) for n, D in sets)
             if metric_hists is not None:
                 metric_hists.append((phase, tag + suffix, hists))
+            if metric_spectra is not None:
+                metric_spectra.extend((phase, tag + suffix, s) for s in spectra)
             return m
 
         g_lr0, d_lr0 = scale_lr(args.g_lr, args.d_lr, args.g_scaling, args.d_scaling, horovod, global_size)
